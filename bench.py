@@ -9,6 +9,8 @@ full training step = encoder fwd + HIP hot path fwd + losses + backward + gradie
 what the first 40 epochs run).  `value` = samples/s of the whole job, inputs resident in HBM.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --full              # + per-kernel roofline / families, exact_f32 and bf16x3 legs, CPU baseline, [comm] (N > 1)
+    python bench.py --dump-outputs DIR  # + DIR/<name>.npy: what the last timed step returned (fixed seeds: same inputs every run)
     python bench.py --config 3          # BASELINE configs[3]: HO3Dv2-shape B=16, 3072+1024 points, IK variant, inference
     python bench.py --config 4          # BASELINE configs[4]: dense eval, 6144+2048 points, f16-MFMA attention, B=8 over 2 GPUs
     python bench.py --branch-mix        # configs[1] with the epoch >= 40 point-branch mix (40 % pre-points, 60 % sdf_infer)
@@ -158,6 +160,21 @@ class KernelTimer:
                 for (n, shape), (c, ms, fl) in rows]
 
 
+def dump_outputs(path, arrays, limit=64 << 20):
+    """`arrays` (name -> tensor) as path/<name>.npy: float64 and integer tensors as float64, the rest as float32.  Past `limit`
+    bytes in all, every array is cut to the same fraction of its elements, picked by a fixed seed (so two runs pick the same ones)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    f32 = lambda t: t == torch.bool or (t.is_floating_point and t != torch.float64)
+    arrs = {k: v.detach().cpu().to(torch.float32 if f32(v.dtype) else torch.float64).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in sorted(arrs.items()):
+        if total > limit:
+            n = max(1, int(a.size * limit / total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,9 +202,21 @@ def main():
     ap.add_argument("--n-hand", type=int, default=None)
     ap.add_argument("--n-obj", type=int, default=None)
     ap.add_argument("--resnet", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP events (roofline, families, kernels), the "
+                         "exact_f32 and bf16x3 legs, the CPU baseline and, with N > 1, the communication diagnostics.  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the result line; the switches below turn single "
+                         "parts of --full off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the model's output dict and the "
+                         "step's loss, and for the training step a fixed seeded sample of the hot path's gradients) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB in all.  That step starts from the initial weights "
+                         "(copied back, and their emulation images rebuilt, with the clock stopped), so the arrays repeat from run "
+                         "to run up to rounding.  In such a run the result line's final_loss is that step's loss at the initial "
+                         "weights, and the pipeline drain before the copy can make ms_per_step read slightly higher than a plain run's")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--bf16x3-leg", type=int, default=1, help="also time 10 steps with HOISDF_EMU_FORM=b3 in a child process (outside the timed region) into `bf16x3`")
-    ap.add_argument("--exact-f32", type=int, default=1, help="also time 10 steps of the exact-f32 path (outside the timed region) into `exact_f32`")
+    ap.add_argument("--bf16x3-leg", type=int, default=1, help="with --full: also time 10 steps with HOISDF_EMU_FORM=b3 in a child process (outside the timed region) into `bf16x3`")
+    ap.add_argument("--exact-f32", type=int, default=1, help="with --full: also time 10 steps of the exact-f32 path (outside the timed region) into `exact_f32`")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--time-every", type=int, default=20, help="record per-kernel HIP events on every n-th timed step (such a step runs single-stream with ~1400 event records: ~10 ms slower than a plain one)")
     ap.add_argument("--force-dist", action="store_true",
@@ -202,6 +231,9 @@ def main():
                     help="host threads for the CPU baseline (32 was the best of 16/32/64/256 probed on the "
                          "2x EPYC 9575F GPU-box host; 256 threads is >10x slower)")
     args = ap.parse_args()
+    if not args.full:              # a plain run: only what the headline line needs
+        args.no_cpu_baseline = args.no_kernel_timing = True
+        args.bf16x3_leg = args.exact_f32 = 0
     dflt = {1: (32, 1536, 512), 3: (16, 3072, 1024), 4: (8 // max(2, args.gpus), 6144, 2048)}[args.config]
     args.batch = args.batch or dflt[0]
     args.n_hand = args.n_hand or dflt[1]
@@ -218,6 +250,11 @@ def main():
         local = 0
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    # MIOpen runs its find again for every convolution of a new process (the shipped find-db records are regenerated), and
+    # times its naive reference kernels there too: ~23 s of the first warm-up step, for solvers that never win (no record of
+    # hoisdf_amd/miopen_db picks one).  Left out of the find, the solvers it chooses from are the ones that can win.
+    for d in ("FWD", "BWD", "WRW"):
+        os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{d}", "0")
     if args.miopen_find:
         from hoisdf_amd import miopen_tuning
         miopen_tuning.enable()
@@ -261,6 +298,13 @@ def main():
         # launch; 1/world of the gradient mean is folded into it
         opt = FusedAdamW(list(model.parameters()), lr=cfg.lr, grad_scale=1.0 / world)
     ops.manual_seed(1000 + rank)   # dropout stream: distinct per rank
+    # --dump-outputs: the dumped (last timed) step starts from the initial weights.  Its outputs are computed before its own update,
+    # so they then depend on the inputs, the seeds and the initial weights only.  After 20+ AdamW steps the weights themselves
+    # carry the run-to-run rounding of the encoder's MIOpen convolutions (solvers found by timing, atomically accumulated weight
+    # gradients), which the steps amplify far beyond rounding.
+    snap = None
+    if args.dump_outputs is not None:
+        snap = [t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
     model._py_random = __import__("random").Random(4321 + rank)      # the branch A / B draw (main/model.py:426)
     if use_dist and world > 1:
         # data-parallel sanity: every rank starts from the same weights and draws different dropout masks
@@ -279,6 +323,7 @@ def main():
         inputs["img"] = inputs["img"].contiguous(memory_format=torch.channels_last)
     epoch_cnt = 1e8 if args.branch_mix else 0          # epoch >= cfg.point_sampling_epoch: p < 0.4 -> A, else B
     branches = {"A": 0, "B": 0}
+    keep = {}                       # --dump-outputs: what the step marked by keep["on"] returned
 
     def train_step():
         reducer.zero_grad()
@@ -288,11 +333,15 @@ def main():
         total.backward()
         reducer.finish()
         opt.step()
+        if keep.get("on"):
+            keep["out"] = {**{k: v.detach() for k, v in out.items() if torch.is_tensor(v)}, "total_loss": total.detach()}
         return total
 
     @torch.no_grad()
     def eval_step():
         out = model(inputs, targets, meta, "eval")                           # main/test.py:126 (dense-lattice sdf_infer)
+        if keep.get("on"):
+            keep["out"] = {k: v for k, v in out.items() if torch.is_tensor(v)}
         return out["hand_joints_out"].sum()
 
     step = train_step if train else eval_step
@@ -348,6 +397,7 @@ def main():
     # step cost 1.7 % of the step (they serialise consecutive kernels), which `value` should not pay on every step
     timed_steps = 0
     model.branch_log = []
+    paused = 0.0
     t0 = time.perf_counter()
     marks = []                                  # host clock after each step's launches were queued (no synchronisation: diagnostics only)
     for i in range(args.steps):
@@ -355,10 +405,21 @@ def main():
         _lib.set_timer(timer if sample else None)
         cfg.overlap_streams = not sample        # event-bracketed steps run single-stream: with the object stack on a second
         timed_steps += int(sample)              # stream a kernel's events would also span the other stream's kernels
+        keep["on"] = args.dump_outputs is not None and i == args.steps - 1
+        if keep["on"]:                          # back to the initial weights (above), outside the clock
+            barrier()
+            tp = time.perf_counter()
+            with torch.no_grad():
+                for t, s0 in zip(list(model.parameters()) + list(model.buffers()), snap):
+                    t.copy_(s0)
+            ops.bump_weight_generation()        # the emulation weight images follow the copy here, not inside the step
+            barrier()
+            paused += time.perf_counter() - tp
         last = step()
         marks.append(time.perf_counter())
     barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
+    keep["on"] = False
     if os.environ.get("HOISDF_BENCH_STEP_LOG") and rank == 0:
         print("host clock per step (ms, launches queued, no sync):", [round(1e3 * (b - a), 1) for a, b in zip([t0] + marks[:-1], marks)],
               "drain %.1f" % (1e3 * (t0 + dt - marks[-1])), file=sys.stderr)
@@ -370,10 +431,24 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
     assert torch.isfinite(last), "non-finite loss"
+    if args.dump_outputs is not None and rank == 0:
+        arrays = keep.pop("out")
+        if train:
+            # what the last step's backward computed is still in .grad (the next step would have zeroed it): a fixed seeded
+            # sample over the hot path's parameters in registration order, frozen ones as zeros.  (The image encoder's are left
+            # out: MIOpen accumulates its weight gradients atomically, and forty layers of ReLU gates carry that rounding to
+            # 4e-3 of the largest gradient from run to run.)
+            import numpy as np
+            with torch.no_grad():
+                hot = [p for n, p in model.named_parameters() if not n.startswith(("backbone_net.", "decoder_net."))]
+                g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in hot])
+                pick = np.sort(np.random.default_rng(1).choice(g.numel(), min(g.numel(), 1 << 20), replace=False))
+                arrays["grad_sample"] = g[torch.from_numpy(pick).to(g.device)]
+        dump_outputs(args.dump_outputs, arrays)
 
     # ---- communication diagnostics (every rank takes part, rank 0 reports; outside the timed region) -----------------------
     comm = None
-    if use_dist and train:
+    if args.full and use_dist and train:
         import torch.distributed as dist
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)

@@ -496,7 +496,7 @@ def test_bench_distributed_path_single_rank_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29641", os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--batch", "4", "--n-hand", "192", "--n-obj", "64", "--resnet", "18", "--no-cpu-baseline",
+           "--warmup", "1", "--batch", "4", "--n-hand", "192", "--n-obj", "64", "--resnet", "18", "--full", "--no-cpu-baseline",
            "--force-dist", "--miopen-find", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -518,7 +518,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", HOISDF_BENCH_ONE_GPU_GLOO="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29643", os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "4", "--n-hand", "192", "--n-obj", "64", "--resnet", "18", "--no-cpu-baseline",
+           "--warmup", "1", "--batch", "4", "--n-hand", "192", "--n-obj", "64", "--resnet", "18", "--full", "--no-cpu-baseline",
            "--miopen-find", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -5,11 +5,11 @@
 # Everything lands under gpurun_out/prof_r04/; copy what should be judged into profiles/.
 R=$PWD; O=$R/gpurun_out/prof_r04; mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --no-cpu-baseline --exact-f32 0 --shape-report > /dev/null 2> $O/shape_report.txt
-python bench.py --config 3 --no-cpu-baseline --exact-f32 0 > $O/bench_config3.json 2> /dev/null
-python bench.py --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4.json 2> /dev/null
-python bench.py --branch-mix --no-cpu-baseline --exact-f32 0 > $O/bench_branch_mix.json 2> /dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --no-cpu-baseline --exact-f32 0 --shape-report > /dev/null 2> $O/shape_report.txt
+python bench.py --full --config 3 --no-cpu-baseline --exact-f32 0 > $O/bench_config3.json 2> /dev/null
+python bench.py --full --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4.json 2> /dev/null
+python bench.py --full --branch-mix --no-cpu-baseline --exact-f32 0 > $O/bench_branch_mix.json 2> /dev/null
 cd /tmp
 HOISDF_TWO_STREAMS=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- \
     python $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --exact-f32 0 --no-kernel-timing > $O/bench_under_rocprof.json 2> /dev/null

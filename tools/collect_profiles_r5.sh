@@ -5,13 +5,13 @@
 # Everything lands under gpurun_out/prof_r05/; copy what should be judged into profiles/.
 R=$PWD; O=$R/gpurun_out/prof_r05; mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --no-cpu-baseline --exact-f32 0 --shape-report > /dev/null 2> $O/shape_report.txt
-python bench.py --config 3 --no-cpu-baseline --exact-f32 0 > $O/bench_config3.json 2> /dev/null
-python bench.py --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4.json 2> /dev/null
-python bench.py --config 4 --f16-attention 0 --no-cpu-baseline --exact-f32 0 > $O/bench_config4_fp32_attention.json 2> /dev/null
-HOISDF_ATTN16=f16 python bench.py --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4_round2_f16_kernel.json 2> /dev/null
-python bench.py --branch-mix --no-cpu-baseline --exact-f32 0 > $O/bench_branch_mix.json 2> /dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --no-cpu-baseline --exact-f32 0 --shape-report > /dev/null 2> $O/shape_report.txt
+python bench.py --full --config 3 --no-cpu-baseline --exact-f32 0 > $O/bench_config3.json 2> /dev/null
+python bench.py --full --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4.json 2> /dev/null
+python bench.py --full --config 4 --f16-attention 0 --no-cpu-baseline --exact-f32 0 > $O/bench_config4_fp32_attention.json 2> /dev/null
+HOISDF_ATTN16=f16 python bench.py --full --config 4 --no-cpu-baseline --exact-f32 0 > $O/bench_config4_round2_f16_kernel.json 2> /dev/null
+python bench.py --full --branch-mix --no-cpu-baseline --exact-f32 0 > $O/bench_branch_mix.json 2> /dev/null
 cd /tmp
 for cfg in default config4; do
   extra=""; marker=""; [ $cfg = config4 ] && extra="--config 4" && marker="vote_loss_fwd_kernel"

@@ -24,11 +24,11 @@ cd $R
 bash tools/pmc_collect.sh $O/pmc_raw > /dev/null 2>&1
 python tools/pmc_fold.py $O/pmc_raw > $O/pmc.json
 cp $O/pmc.json $R/profiles/r06_pmc.json
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 --shape-report > /dev/null 2> $O/shape_report.txt
-python bench.py --config 3 --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_config3.json 2> /dev/null
-python bench.py --config 4 --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_config4.json 2> /dev/null
-python bench.py --branch-mix --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_branch_mix.json 2> /dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 --shape-report > /dev/null 2> $O/shape_report.txt
+python bench.py --full --config 3 --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_config3.json 2> /dev/null
+python bench.py --full --config 4 --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_config4.json 2> /dev/null
+python bench.py --full --branch-mix --no-cpu-baseline --exact-f32 0 --bf16x3-leg 0 > $O/bench_branch_mix.json 2> /dev/null
 # the round-5 tree on the same box (ab/r5tree: git archive of 811360c + its own library), interleaved quick lines
 [ -d ab/r5tree ] && bash ab/ab_r5.sh > $O/same_box_ab_vs_round5.txt 2>&1
 # this round's encoder-side / inference-side changes against their switches, same box, alternating
