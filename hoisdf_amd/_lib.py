@@ -112,6 +112,45 @@ class MlpGrads(C.Structure):
     _fields_ = [("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS)]
 
 
+POSE_MAX_LAYERS = 12
+
+
+class PoseDesc(C.Structure):
+    """include/hoisdf.h hoisdf_pose_desc"""
+    _fields_ = [("B", C.c_int), ("num_samp_hand", C.c_int), ("num_samp_obj", C.c_int), ("bins_n", C.c_int), ("img_h", C.c_int),
+                ("img_w", C.c_int), ("hand_sdf_scale", C.c_float), ("obj_sdf_scale", C.c_float), ("clamping_distance", C.c_float),
+                ("hidden_dim", C.c_int), ("nheads", C.c_int), ("dim_feedforward", C.c_int), ("enc_layers", C.c_int),
+                ("dec_layers", C.c_int), ("C", C.c_int), ("use_inverse_kinematics", C.c_int), ("pre_norm", C.c_int),
+                ("classifier_branch", C.c_int), ("attention", C.c_int)]
+
+
+class SdfDecoderParams(C.Structure):
+    """include/hoisdf.h hoisdf_sdf_decoder_params"""
+    _fields_ = [("weight_v", C.c_void_p * 4), ("weight_g", C.c_void_p * 4), ("bias", C.c_void_p * 4),
+                ("linh4_weight", C.c_void_p), ("linh4_bias", C.c_void_p)]
+
+
+class PoseWeights(C.Structure):
+    """include/hoisdf.h hoisdf_pose_weights"""
+    _fields_ = [("linear_sdfin", Mlp), ("hand_sdf_decoder", SdfDecoderParams), ("obj_sdf_decoder", SdfDecoderParams),
+                ("linear_transformerin", Mlp), ("hand_sigmoid_beta", C.c_void_p), ("obj_sigmoid_beta", C.c_void_p),
+                ("hand_encoder", EncoderLayerWeights * POSE_MAX_LAYERS), ("obj_encoder", EncoderLayerWeights * POSE_MAX_LAYERS),
+                ("hand_decoder", DecoderLayerWeights * POSE_MAX_LAYERS), ("mano_query_embed", C.c_void_p),
+                ("linear_pose", Mlp), ("linear_shape", Mlp), ("linear_handvote", Mlp), ("linear_handcls", Mlp),
+                ("linear_obj_rot", Mlp), ("linear_obj_rel_trans", Mlp),
+                ("mano_shapedirs", C.c_void_p), ("mano_posedirs", C.c_void_p), ("mano_weights", C.c_void_p),
+                ("mano_v_template", C.c_void_p), ("mano_j_regressor", C.c_void_p), ("mano_hands_mean", C.c_void_p)]
+
+
+_POSE_OUT = ("hand_joints_out", "obj_rot_out", "obj_trans_out", "mano_mesh_out", "mano_joints_out", "mano_shape_out",
+             "hand_points_out", "obj_points_out", "hand_sdf_out", "obj_sdf_out")
+
+
+class PoseOutputs(C.Structure):
+    """include/hoisdf.h hoisdf_pose_outputs"""
+    _fields_ = [(n, C.c_void_p) for n in _POSE_OUT]
+
+
 _P, _I, _L, _F, _U64, _D = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_double
 _PYR = C.POINTER(Pyramid)
 _SDFW = C.POINTER(SdfWeights)
@@ -200,6 +239,9 @@ SIGNATURES: Dict[str, List] = {
     "hoisdf_heads_vote_bwd": [_P, _P, _P, _P, _P, _F, _P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P],
     "hoisdf_point_loss_fwd": [_P, _P, _L, _L, _I, _L, _I, _F, _F, _F, _P, _P, _P],
     "hoisdf_point_loss_bwd": [_P, _P, _L, _L, _I, _L, _I, _F, _F, _F, _P, _P, _P],
+    "hoisdf_pose_prepare": [_P, _P, _P, _L, _P],
+    "hoisdf_pose_infer_begin": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "hoisdf_pose_infer": [_P, _P, _PYR, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
 }
 _RET = {"hoisdf_version": C.c_char_p, "hoisdf_last_error": C.c_char_p}
 _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I], None), "hoisdf_get_gemm_emu": ([], C.c_int), "hoisdf_get_deterministic": ([], C.c_int),
@@ -233,7 +275,9 @@ _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I]
           "hoisdf_attention_f16_workspace": ([_I, _I, _I], C.c_long),
           "hoisdf_attention_bf16x2_workspace": ([_I, _I, _I, _I], C.c_long),
           "hoisdf_attention_emu_workspace": ([_I, _I, _I, _I, _I], C.c_long),
-          "hoisdf_attention_bwd_emu_workspace": ([_I, _I, _I, _I, _I], C.c_long)}
+          "hoisdf_attention_bwd_emu_workspace": ([_I, _I, _I, _I, _I], C.c_long),
+          "hoisdf_pose_prepared_bytes": ([_P], C.c_long),
+          "hoisdf_pose_infer_workspace": ([_P, _P], C.c_long)}
 
 _lib = None
 

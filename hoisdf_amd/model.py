@@ -59,6 +59,8 @@ def get_manoshape_memory_mask(cfg=_global_cfg):
 # per-model cache of the hoisdf_sdf_query_fwd weight descriptors (ctypes structs of raw device pointers): kept OUT of the
 # module's __dict__ so that copy.deepcopy(model) / torch.save(model) never see them
 _SDFQ_CACHE = weakref.WeakKeyDictionary()
+# per-model cache of the prepared blob of the whole-model C entry (ops.PosePrepared), keyed like the folds above
+_POSE_CACHE = weakref.WeakKeyDictionary()
 
 
 class Model(nn.Module):
@@ -164,6 +166,9 @@ class Model(nn.Module):
         """drop the cached weight-norm folds (call after changing SDF-MLP weights in a way torch's version counters and
         FusedAdamW cannot see, e.g. a foreign kernel writing the parameters in place)"""
         _SDFQ_CACHE.pop(self, None)
+        ent = _POSE_CACHE.get(self)
+        if ent is not None:
+            ent["key"] = None            # the next infer_native prepares again (the build counter keeps counting)
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
@@ -463,9 +468,157 @@ class Model(nn.Module):
                 t.record_stream(cur)
         return loss, out
 
+    # ---- the same stage through ONE C-ABI call (include/hoisdf.h hoisdf_pose_infer; opt-in) ------------------------------
+    def native_infer_enabled(self) -> bool:
+        """cfg.native_infer (default False) or HOISDF_INFER=native: Model.forward in eval mode runs infer_native instead of hot_path"""
+        return bool(getattr(self.cfg, "native_infer", False)) or os.environ.get("HOISDF_INFER", "") == "native"
+
+    def _pose_desc(self, B, C_):
+        from ._lib import PoseDesc
+        c = self.cfg
+        return PoseDesc(B=B, num_samp_hand=c.num_samp_hand, num_samp_obj=c.num_samp_obj, bins_n=c.bins_n, img_h=c.input_img_shape[0],
+                        img_w=c.input_img_shape[1], hand_sdf_scale=c.hand_sdf_scale, obj_sdf_scale=c.obj_sdf_scale,
+                        clamping_distance=c.ClampingDistance, hidden_dim=c.hidden_dim, nheads=c.nheads, dim_feedforward=c.dim_feedforward,
+                        enc_layers=c.enc_layers, dec_layers=c.dec_layers, C=C_, use_inverse_kinematics=int(c.use_inverse_kinematics),
+                        pre_norm=int(c.pre_norm), classifier_branch=int(c.ClassifierBranch), attention=2 if ops.attention_emu() else 0)
+
+    def _pose_weights(self):
+        """hoisdf_pose_weights from the module's own parameters -> (struct, the tensors it points to)"""
+        from ._lib import PoseWeights
+        w, keep = PoseWeights(), []
+
+        def t(x):
+            x = x.detach().float().contiguous()
+            keep.append(x)
+            return x.data_ptr()
+
+        def mlp(dst, m, act_last):
+            dst.n_layers, dst.act_last = len(m.layers), int(act_last)
+            dst.dims[0] = m.layers[0].weight.shape[1]
+            for i, l in enumerate(m.layers):
+                dst.dims[i + 1] = l.weight.shape[0]
+                dst.w[i], dst.b[i] = t(l.weight), t(l.bias)
+
+        def sdf_dec(dst, dec):
+            for i in range(4):
+                l = getattr(dec, f"linh{i}")
+                dst.weight_v[i], dst.weight_g[i], dst.bias[i] = t(l.weight_v), t(l.weight_g), t(l.bias)
+            dst.linh4_weight, dst.linh4_bias = t(dec.linh4.weight), t(dec.linh4.bias)
+
+        def enc(dst, stack):
+            n = stack.inter_norm
+            for i, l in enumerate(stack.layers):
+                a, d = l.self_attn, dst[i]
+                d.w_in, d.b_in, d.w_out, d.b_out = t(a.in_proj_weight), t(a.in_proj_bias), t(a.out_proj.weight), t(a.out_proj.bias)
+                d.g1, d.be1, d.w1, d.b1 = t(l.norm1.weight), t(l.norm1.bias), t(l.linear1.weight), t(l.linear1.bias)
+                d.w2, d.b2, d.g2, d.be2 = t(l.linear2.weight), t(l.linear2.bias), t(l.norm2.weight), t(l.norm2.bias)
+                d.g3, d.be3 = t(n.weight), t(n.bias)
+
+        mlp(w.linear_sdfin, self.linear_sdfin, True)
+        sdf_dec(w.hand_sdf_decoder, self.hand_sdf_decoder)
+        sdf_dec(w.obj_sdf_decoder, self.obj_sdf_decoder)
+        mlp(w.linear_transformerin, self.linear_transformerin, True)
+        w.hand_sigmoid_beta, w.obj_sigmoid_beta = t(self.hand_sigmoid_beta), t(self.obj_sigmoid_beta)
+        enc(w.hand_encoder, self.hand_transformer.encoder)
+        enc(w.obj_encoder, self.obj_transformer.encoder)
+        dn = self.hand_transformer.decoder.norm
+        for i, l in enumerate(self.hand_transformer.decoder.layers):
+            sa, ca, d = l.self_attn, l.multihead_attn, w.hand_decoder[i]
+            d.sa_w_in, d.sa_b_in, d.sa_w_out, d.sa_b_out = t(sa.in_proj_weight), t(sa.in_proj_bias), t(sa.out_proj.weight), t(sa.out_proj.bias)
+            d.ca_w_in, d.ca_b_in, d.ca_w_out, d.ca_b_out = t(ca.in_proj_weight), t(ca.in_proj_bias), t(ca.out_proj.weight), t(ca.out_proj.bias)
+            d.w1, d.b1, d.w2, d.b2 = t(l.linear1.weight), t(l.linear1.bias), t(l.linear2.weight), t(l.linear2.bias)
+            d.g1, d.be1, d.g2, d.be2, d.g3, d.be3 = (t(x) for x in (l.norm1.weight, l.norm1.bias, l.norm2.weight, l.norm2.bias,
+                                                                      l.norm3.weight, l.norm3.bias))
+            d.g4, d.be4 = t(dn.weight), t(dn.bias)
+        w.mano_query_embed = t(self.mano_query_embed.weight)
+        mlp(w.linear_shape, self.linear_shape, False)
+        mlp(w.linear_handvote, self.linear_handvote, False)
+        mlp(w.linear_handcls, self.linear_handcls, False)
+        mlp(w.linear_obj_rot, self.linear_obj_rot, False)
+        mlp(w.linear_obj_rel_trans, self.linear_obj_rel_trans, False)
+        if not self.cfg.use_inverse_kinematics:
+            mlp(w.linear_pose, self.linear_pose, False)
+            ml = self.mano_head.mano_layer
+            if ml.kernel_assets() is None:
+                raise RuntimeError("infer_native needs this package's ManoLayer on the GPU, centred on the wrist, with a zero hand mean "
+                                   "(the configuration of the reference, main/model.py:735-742)")
+            w.mano_shapedirs, w.mano_posedirs, w.mano_weights = t(ml.th_shapedirs), t(ml.th_posedirs), t(ml.th_weights)
+            w.mano_v_template, w.mano_j_regressor, w.mano_hands_mean = t(ml.th_v_template), t(ml.th_J_regressor), t(ml.th_hands_mean)
+        return w, keep
+
+    def _pose_prepared(self, B, C_, device):
+        """the prepared blob (weight copies, weight-norm folds, weight images, MANO image, floored betas, target mask), rebuilt only
+        when a parameter, the batch size or an arithmetic switch changed - the key of the SDF-query folds, over every parameter"""
+        ps = [p for n, p in self.named_parameters() if not n.startswith(("backbone_net", "decoder_net"))] + \
+             [b for n, b in self.named_buffers() if n.startswith("mano_head")]
+        key = (B, C_, str(device), ops._WEIGHT_GEN[0], ops.gemm_emu(), ops.attention_emu()) + tuple((p.data_ptr(), p._version) for p in ps)
+        ent = _POSE_CACHE.get(self)
+        if ent is None:
+            ent = _POSE_CACHE[self] = {"key": None, "prepared": None, "builds": 0}
+        if ent["key"] != key:
+            w, keep = self._pose_weights()
+            ent["builds"] += 1
+            ent["prepared"] = ops.PosePrepared(self._pose_desc(B, C_), w, device, ent["builds"])
+            ent["key"] = key
+            del keep            # (the blob holds its own copies; the copies above are ordered on the current stream)
+        return ent["prepared"]
+
+    @torch.no_grad()
+    def infer_native(self, pyr, meta_info, counts=None, debug=False) -> Dict[str, torch.Tensor]:
+        """The eval forward of hot_path through ONE C-ABI call (hoisdf_pose_infer): pyramid + camera inputs + boxes ->
+        hand_joints_out, obj_rot_out, obj_trans_out and mano_mesh_out + mano_joints_out (or mano_shape_out for the IK variant),
+        same keys and shapes as hot_path(..., "eval")'s outputs.  No losses, no ground-truth MANO outputs.  ``counts``: what
+        infer_native_begin queued ahead of the encoder.  The default arithmetic only (cfg.attention_f16_eval is not offered)."""
+        c = self.cfg
+        pyr = self._pyramid(pyr)
+        root = meta_info["mano_root"]
+        ops._chk(root, self.hand_sigmoid_beta)          # GPU tensors only: there is no CPU form of this path
+        prepared = self._pose_prepared(root.shape[0], pyr.C, root.device)
+        two = bool(getattr(c, "overlap_streams", True)) and os.environ.get("HOISDF_TWO_STREAMS", "1") != "0" and not ops.deterministic()
+        side = None
+        if two:
+            if getattr(self, "_side_stream", None) is None:
+                prio = 0 if os.environ.get("HOISDF_SIDE_PRIORITY") == "0" else -1
+                self._side_stream = torch.cuda.Stream(device=root.device, priority=prio)
+            side = self._side_stream
+        return ops.pose_infer(prepared, pyr, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
+                              meta_info["bbox_obj"], counts, side, debug)
+
+    def infer_native_begin(self, meta_info, C_=None):
+        """queue both survivor counts of infer_native (hoisdf_pose_infer_begin) - ahead of the image encoder, as infer_counts_begin"""
+        root = meta_info["mano_root"]
+        prepared = self._pose_prepared(root.shape[0], self.cfg.mutliscale_dim if C_ is None else C_, root.device)
+        return ops.PoseInferCounts(prepared.desc, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
+                                   meta_info["bbox_obj"])
+
+    def _forward_native(self, inputs, targets, meta_info):
+        """eval forward with the switch on: the encoder in PyTorch, then infer_native; dexycb keeps its ground-truth MANO outputs"""
+        c = self.cfg
+        if getattr(c, "gemm_emu", None) is not None:
+            ops.set_gemm_emu(bool(c.gemm_emu))
+        if getattr(c, "attention_emu", None) is not None:
+            ops.set_attention_emu(bool(c.attention_emu))
+        with torch.no_grad():
+            counts = self.infer_native_begin(meta_info, self.linear_sdfin.layers[0].weight.shape[1])
+            img_feat, skips = self.backbone_net(inputs["img"])
+            feature_pyramid, decoder_out = self.decoder_net(img_feat, skips)
+            out = self.infer_native(self._pyramid(feature_pyramid), meta_info, counts)
+            if c.dataset == "dexycb":
+                if not c.use_inverse_kinematics:
+                    gv, gj, _ = ops.mano_gt(targets["mano_param"], self.mano_head.mano_layer.kernel_assets())
+                    out["mano_joints_gt_out"], out["mano_mesh_gt_out"] = gj, gv
+                out["joint_heatmap_out"] = decoder_out[:, 0]
+                out["hand_seg_gt_out"] = targets["hand_seg"]
+                out["hand_seg_pred_out"] = decoder_out[:, 1]
+                out["obj_seg_gt_out"] = targets["obj_seg"]
+                out["obj_seg_pred_out"] = decoder_out[:, 2]
+        return out
+
     def forward(self, inputs, targets, meta_info, mode, epoch_cnt=1e8, batch_ratio=0):
         """reference :357-665."""
         c = self.cfg
+        if mode != "train" and not self.training and self.native_infer_enabled():
+            return self._forward_native(inputs, targets, meta_info)
         branch_a = self.draw_branch(mode, epoch_cnt)                                  # :426-427, drawn ahead of the encoder
         infer_counts = None if branch_a else self.infer_counts_begin(meta_info)       # read back under the encoder's kernels
         img_feat, skips = self.backbone_net(inputs["img"])                            # :367-368 (PyTorch / MIOpen)

@@ -2271,3 +2271,90 @@ def bn_act(x, weight, bias, running_mean, running_var, training: bool, momentum,
     training: batch statistics, running statistics updated in place as torch.nn.functional.batch_norm does;
     otherwise the running statistics normalise (no gradient path: evaluation)."""
     return _BnAct.apply(x, weight, bias, residual, running_mean, running_var, bool(training), momentum, float(eps), bool(relu))
+
+
+# ---------------------------------------------------------------------------------------------
+# whole-model inference behind one C entry (include/hoisdf.h hoisdf_pose_*; csrc/pose_infer.hip)
+# ---------------------------------------------------------------------------------------------
+class PosePrepared:
+    """The prepared blob of hoisdf_pose_prepare for one (descriptor, weights) pair: device memory + the descriptor it was built
+    for.  ``version`` counts the builds of the owning model (tests pin that a second frame does not prepare again)."""
+
+    def __init__(self, desc, weights, device, version: int = 0):
+        nbytes = lib().hoisdf_pose_prepared_bytes(C.addressof(desc))
+        if nbytes < 0:
+            raise ValueError(lib().hoisdf_last_error().decode())
+        self.desc, self.version = desc, version
+        self.blob = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        call("hoisdf_pose_prepare", C.addressof(desc), C.addressof(weights), _p(self.blob), nbytes, _st())
+        self.stream = torch.cuda.current_stream(device)
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+
+
+class PoseInferCounts:
+    """hoisdf_pose_infer_begin: the queued survivor counts of both fields (2 B words: hand, object), their page-locked host copy and
+    the event behind the copy - as SdfInferCounts, for the whole-model entry."""
+
+    def __init__(self, desc, root, ocen, cam_intr, bbox_hand, bbox_obj):
+        self.args = tuple(t.contiguous() for t in (root, ocen, cam_intr, bbox_hand, bbox_obj))
+        _chk(*self.args)
+        B = root.shape[0]
+        self.B = B
+        self.counts = torch.empty(2 * B, device=root.device, dtype=torch.int32)
+        free = _PINNED_I32.setdefault(2 * B, [])
+        self.host = free.pop() if free else torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
+        call("hoisdf_pose_infer_begin", C.addressof(desc), *(_p(t) for t in self.args), _p(self.counts), C.c_void_p(self.host.data_ptr()), _st())
+        self.event = torch.cuda.Event()
+        self.event.record()
+        self._list = None
+
+    def wait(self):
+        if self._list is None:
+            self.event.synchronize()
+            self._list = self.host.tolist()
+            _PINNED_I32[2 * self.B].append(self.host)
+        return self._list
+
+
+@torch.no_grad()
+def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr, bbox_hand, bbox_obj, counts: Optional[PoseInferCounts] = None,
+               side_stream=None, debug: bool = False):
+    """hoisdf_pose_infer: the eval forward of everything after the image encoder in ONE C-ABI call -> dict of the ``*_out`` tensors
+    (with ``debug`` also the selected points and their SDF values).  Raises ValueError when a sample has fewer lattice survivors
+    than requested points (nothing is launched then)."""
+    from ._lib import PoseOutputs
+    d = prepared.desc
+    dev = root.device
+    if counts is None:
+        counts = PoseInferCounts(d, root, ocen, cam_intr, bbox_hand, bbox_obj)
+    root, ocen, cam_intr, bbox_hand, bbox_obj = counts.args
+    B, nh, no = d.B, d.num_samp_hand, d.num_samp_obj
+    e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+    out = {"hand_joints_out": e(B, 20, 3), "obj_rot_out": e(B, no, 3), "obj_trans_out": e(B, no, 3)}
+    if d.use_inverse_kinematics:
+        out["mano_shape_out"] = e(B, 10)
+    else:
+        out["mano_mesh_out"], out["mano_joints_out"] = e(B, 778, 3), e(B, 21, 3)
+    if debug:
+        out.update(hand_points_out=e(B, nh, 3), obj_points_out=e(B, no, 3), hand_sdf_out=e(B, nh), obj_sdf_out=e(B, no))
+    cl = counts.wait()          # the one host read of the path: everything that does not need the counts is done
+    counts_h = (C.c_int32 * (2 * B))(*cl)
+    for kind, n, part in (("hand", nh, cl[:B]), ("obj", no, cl[B:])):
+        short = [b for b in range(B) if part[b] < n]
+        if short:
+            raise ValueError(f"sdf_infer({kind}): sample {short[0]} has only {part[short[0]]} lattice points inside its bbox, fewer "
+                             f"than num_points={n} (the reference fails at main/model.py:348)")
+    nbytes = lib().hoisdf_pose_infer_workspace(C.addressof(d), C.addressof(counts_h))
+    if nbytes < 0:
+        raise ValueError(lib().hoisdf_last_error().decode())
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    o = PoseOutputs(**{k: v.data_ptr() for k, v in out.items()})
+    cur = torch.cuda.current_stream(dev)
+    if prepared.stream != cur:
+        cur.wait_event(prepared.event)
+    s = pyr.struct()
+    call("hoisdf_pose_infer", C.addressof(d), _p(prepared.blob), C.byref(s), _p(root), _p(ocen), _p(cam_intr), _p(bbox_hand), _p(bbox_obj),
+         _p(counts.counts), C.addressof(counts_h), C.addressof(o), _p(ws), nbytes,
+         None if side_stream is None else C.c_void_p(side_stream.cuda_stream), _st())
+    return out          # (the call returns with the current stream ordered behind the side stream's work: no record_stream needed)

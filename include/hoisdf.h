@@ -742,6 +742,93 @@ int hoisdf_mano_head_bwd(const float* pose6d, const float* betas, int hands, con
                          const float* g_loss_sums, const float* g_verts, const float* g_joints, const float* g_rot,
                          float* d_pose6d, float* d_betas, void* stream);
 
+/* ---- whole-model inference: the stage after the image encoder as ONE entry ---------------------------------------------
+ * reference: the eval forward of Model.forward behind decoder_net (main/model.py:424-662, the sdf_infer branch :462-481): feature
+ * pyramid + camera inputs + boxes in, hand joints / object pose / MANO mesh out.  No losses, no targets, dropout off.  The host
+ * composite (csrc/pose_infer.hip) issues the coarse entries above in the order hoisdf_amd/model.py Model.hot_path does, so the
+ * same shape takes the same kernel on either host; only what inference reads is computed (heads and stack norms on the LAST
+ * layer's rows only).  Call sequence of a host (INTEGRATION.md "the whole pose stage from C"):
+ *   once   : hoisdf_pose_prepared_bytes -> allocate -> hoisdf_pose_prepare (everything that depends on the weights alone: copies of
+ *            the parameters, the weight-norm folds of both SDF decoders in the layouts of hoisdf_sdf_weights, the weight images of
+ *            the emulated GEMMs in the process's form, the MANO table image, both sigmoid_beta floored at 2e-3, the MANO target
+ *            mask, the zero decoder input).  The blob is self-contained: the caller's weight buffers may go once the stream has
+ *            executed the call.  Rebuild it when a weight changes.
+ *   frame  : hoisdf_pose_infer_begin (queues both survivor counts, returns without waiting: issue it ahead of the image encoder)
+ *            -> wait until `stream` has executed it -> hoisdf_pose_infer_workspace(desc, counts_host) -> hoisdf_pose_infer.
+ * The 2 B survivor counts are the one device -> host read of the path (counts [0, B) = hand field, [B, 2 B) = object field;
+ * counts_host is page-locked host memory). */
+typedef struct hoisdf_pose_desc {
+  int B;                           /* samples */
+  int num_samp_hand, num_samp_obj; /* query points per field (cfg.num_samp_hand / num_samp_obj) */
+  int bins_n;                      /* lattice resolution of sdf_infer (cfg.bins_n) */
+  int img_h, img_w;                /* cfg.input_img_shape */
+  float hand_sdf_scale, obj_sdf_scale, clamping_distance;   /* cfg.hand_sdf_scale / obj_sdf_scale / ClampingDistance */
+  int hidden_dim;                  /* 256: the SDF decoders and the token layout [3 | 30 | 223] are built for it */
+  int nheads;                      /* hidden_dim / 64 (the attention kernels hold heads of 64) */
+  int dim_feedforward;
+  int enc_layers;                  /* hand encoder depth; the object encoder has enc_layers / 2 (main/model.py:712-720) */
+  int dec_layers;
+  int C;                           /* pyramid channels (992 / 3968) */
+  int use_inverse_kinematics;      /* 1: one decoder query, mano_shape_out only, no MANO head (main/model.py:595-597) */
+  int pre_norm;                    /* cfg.pre_norm: refused (the coarse layer entries are post-norm) */
+  int classifier_branch;           /* cfg.ClassifierBranch: the class logits are read by nothing in this path; accepted, no effect */
+  int attention;                   /* 0: exact-f32 attention kernels; 2: emulated fp32 (the default of hoisdf_encoder_layer_desc) */
+} hoisdf_pose_desc;
+#define HOISDF_POSE_MAX_LAYERS 12
+/* hand_sdf_decoder.* / obj_sdf_decoder.* as checkpointed (torch weight_norm, legacy naming) */
+typedef struct hoisdf_sdf_decoder_params {
+  const float* weight_v[4];        /* linh0 .. linh3: [512][289], [223][512], [512][512], [512][512] */
+  const float* weight_g[4];        /* [512], [223], [512], [512] */
+  const float* bias[4];
+  const float *linh4_weight, *linh4_bias;   /* [1][512], [1] */
+} hoisdf_sdf_decoder_params;
+/* One pointer per parameter of the path, named after the checkpoint keys (tests/golden/g10_state_dict_schema.json).  Image fields of
+ * the member structs are ignored (the prepared blob carries its own). */
+typedef struct hoisdf_pose_weights {
+  hoisdf_mlp linear_sdfin;                 /* C -> 512 -> 256, ReLU after both */
+  hoisdf_sdf_decoder_params hand_sdf_decoder, obj_sdf_decoder;
+  hoisdf_mlp linear_transformerin;         /* C -> 1024 -> 512 -> 256 -> hidden_dim - 33, ReLU after all four */
+  const float *hand_sigmoid_beta, *obj_sigmoid_beta;        /* [1] each */
+  hoisdf_encoder_layer_weights hand_encoder[HOISDF_POSE_MAX_LAYERS];   /* hand_transformer.encoder.layers.i; g3 / be3 = encoder.inter_norm */
+  hoisdf_encoder_layer_weights obj_encoder[HOISDF_POSE_MAX_LAYERS];    /* obj_transformer.encoder.layers.i (enc_layers / 2 of them) */
+  hoisdf_decoder_layer_weights hand_decoder[HOISDF_POSE_MAX_LAYERS];   /* hand_transformer.decoder.layers.i; g4 / be4 = decoder.norm */
+  const float* mano_query_embed;           /* [17][hidden_dim], or [1][hidden_dim] with use_inverse_kinematics */
+  hoisdf_mlp linear_pose;                  /* hidden -> hidden -> hidden -> 6 (unused with use_inverse_kinematics) */
+  hoisdf_mlp linear_shape;                 /* hidden -> hidden -> hidden -> 10 */
+  hoisdf_mlp linear_handvote;              /* hidden -> hidden -> hidden -> hidden -> 60 */
+  hoisdf_mlp linear_handcls;               /* hidden -> hidden -> hidden -> 20 */
+  hoisdf_mlp linear_obj_rot;               /* hidden -> hidden -> hidden -> 3 */
+  hoisdf_mlp linear_obj_rel_trans;         /* hidden -> hidden -> hidden -> 3 */
+  /* MANO assets (unused with use_inverse_kinematics): what hoisdf_mano_prepare / hoisdf_mano_head_fwd take; hands_mean must be zero */
+  const float *mano_shapedirs, *mano_posedirs, *mano_weights, *mano_v_template, *mano_j_regressor, *mano_hands_mean;
+} hoisdf_pose_weights;
+typedef struct hoisdf_pose_outputs {
+  float* hand_joints_out;          /* [B][20][3] */
+  float* obj_rot_out;              /* [B][num_samp_obj][3] */
+  float* obj_trans_out;            /* [B][num_samp_obj][3] */
+  float* mano_mesh_out;            /* [B][778][3]  (not with use_inverse_kinematics) */
+  float* mano_joints_out;          /* [B][21][3]   (not with use_inverse_kinematics) */
+  float* mano_shape_out;           /* [B][10]      (use_inverse_kinematics only) */
+  /* optional debug outputs (NULL = skipped): the selected points (scaled SDF frame) and their clamped SDF values */
+  float *hand_points_out, *obj_points_out;   /* [B][num_samp_*][3] */
+  float *hand_sdf_out, *obj_sdf_out;         /* [B][num_samp_*] */
+} hoisdf_pose_outputs;
+long hoisdf_pose_prepared_bytes(const hoisdf_pose_desc* desc);
+int hoisdf_pose_prepare(const hoisdf_pose_desc* desc, const hoisdf_pose_weights* weights, void* prepared, long prepared_bytes,
+                        void* stream);
+int hoisdf_pose_infer_begin(const hoisdf_pose_desc* desc, const float* center_hand, const float* center_obj, const float* cam_intr,
+                            const float* bbox_hand, const float* bbox_obj, int32_t* counts_device, int32_t* counts_host,
+                            void* stream);
+long hoisdf_pose_infer_workspace(const hoisdf_pose_desc* desc, const int32_t* counts_host);
+/* Only enqueues.  side_stream == NULL: everything on `stream`; otherwise the object-point work, the object encoder stack with its
+ * heads and the MANO head go to side_stream, forked and joined with events as hoisdf_amd/model.py does, and the call returns with
+ * `stream` ordered behind all of it.  The results do not depend on side_stream.  A sample with fewer survivors than requested
+ * points is refused (HOISDF_ERR_TOO_FEW) before anything is launched.  prepared / workspace: 256-byte aligned device memory. */
+int hoisdf_pose_infer(const hoisdf_pose_desc* desc, const void* prepared, const hoisdf_pyramid* pyr, const float* center_hand,
+                      const float* center_obj, const float* cam_intr, const float* bbox_hand, const float* bbox_obj,
+                      const int32_t* counts_device, const int32_t* counts_host, const hoisdf_pose_outputs* outputs,
+                      void* workspace, long workspace_bytes, void* side_stream, void* stream);
+
 /* ---- (f4) auxiliary image losses of the encoder outputs ---------------------------------------------------
  * reference: main/model.py:128-143 (render_gaussian_heatmap) and :404-422 (MSELoss / BCELoss with reduction none).
  * dec = decoder_out (B, 3, H, W) [heat-map, hand seg, object seg] with element strides (sb, sc, sh, sw) - NCHW or
