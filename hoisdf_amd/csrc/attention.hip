@@ -909,11 +909,9 @@ extern "C" int hoisdf_attention_fwd(const float* q, int ldq, const float* k, int
   HOISDF_REQUIRE(o && ldo >= H * DH && (ldo & 3) == 0 && ((uintptr_t)o & 15) == 0, HOISDF_ERR_INVALID,
                  "attention_fwd: bad output");
   if (Lq <= 32) {
-    // (b, head) pairs x key splits ~ 256 blocks, a split = at least 16 key tiles (two per wave); HOISDF_FEWQ_SPLIT=0: never split
-    static int split_on = -1;
-    if (split_on < 0) { const char* e = getenv("HOISDF_FEWQ_SPLIT"); split_on = (e && atoi(e) == 0) ? 0 : 1; }
+    // (b, head) pairs x key splits ~ 256 blocks, a split = at least 16 key tiles (two per wave)
     const int ntiles = cdiv(kv_len, 32);
-    int nsplit = split_on ? min(max(1, 256 / (B * H)), max(1, ntiles / 16)) : 1;
+    int nsplit = min(max(1, 256 / (B * H)), max(1, ntiles / 16));
     float* part = nsplit > 1 ? reinterpret_cast<float*>(mag_scratch(as_stream(stream), (long)B * H * nsplit * (DH + 2) * 32)) : nullptr;
     if (!part) nsplit = 1;
     hipLaunchKernelGGL(attn_fwd_fewq_kernel, dim3(B * H, nsplit), dim3(64 * FEWQ_WAVES), 0, as_stream(stream), a, part);
@@ -941,8 +939,7 @@ extern "C" int hoisdf_attention_bwd(const float* q, int ldq, const float* k, int
                  HOISDF_ERR_INVALID, "attention_bwd: bad leading dims / alignment");
   hipStream_t st = as_stream(stream);
   const long ng = (long)B * Lq * H;
-  static const int env_mode = [] { const char* e = getenv("HOISDF_ATTN_BWD"); return (e && e[0] == 's') ? 0 : 1; }();
-  const int mode = deterministic_mode() ? 0 : env_mode;        // deterministic: the two-kernel form (no dQ atomics)
+  const int mode = deterministic_mode() ? 0 : 1;               // deterministic: the two-kernel form (no dQ atomics)
   // delta = rowsum(dO * O); in fused mode the same pass clears dq, which the fused kernel accumulates with atomics
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((ng * 16 + 255) / 256)), dim3(256), 0, st, a, delta, mode);
   if (int rc = check_launch("attention_delta")) return rc;

@@ -9,13 +9,10 @@
 //   pre-pass  : f32 head slices -> bf16 planes, row-major [bh][Lp][64] and (V only) transposed [bh][64][Lp] (Q pre-scaled by
 //               log2(e)/8: softmax in the log2 domain, the LSE convention of attention.hip)
 //   forward   : block = 128 queries (lane = query), streams 32-key tiles of K rows / V^T:  S^T = K.Q^T, O^T += V^T.P^T
-//   backward  : ONE pass, 5 GEMM-equivalents: block = 128 keys in 8 waves of 16 (lane = key: K, V fragments and dK, dV
-//               accumulators in registers), streams 32-query tiles of Q / dO rows (the transposed fragments come out of the
-//               same tiles through ds_read_b64_tr_b16):  S = Q.K^T, dP = dO.V^T,
-//               dV^T += dO^T.Pd, dK^T += Q^T.dS; every wave drops its dS block (bf16 triples) into a shared LDS tile
-//               T[32 q][128 keys], and each wave then contracts T with the block's K rows over all 128 keys for one 16 x 16
-//               tile of the block's 32 x 64 dQ contribution.  It goes to a per-key-block partial buffer [kb][bh][q][64]; a
-//               reduce pass sums the key blocks in order: no atomics anywhere, run-to-run identical.
+//   backward  : ONE pass, 5 GEMM-equivalents (attention_emu_bwd4.hip; the f16x2 form: attention_emu_bwd4h.hip): block = 128 keys
+//               (lane = key: K, V fragments and dK, dV accumulators in registers), streams 32-query tiles of Q / dO rows.  Its dQ
+//               contribution goes to a per-key-block partial buffer [kb][bh][q][64]; a reduce pass (here) sums the key blocks in
+//               order: no atomics anywhere, run-to-run identical.
 // The dropout mask is the same function of (seed, query, key) as in the f32 kernels.
 #include <stdlib.h>
 
@@ -39,7 +36,6 @@ constexpr int TPH = 36;             // bf16 per row of a transposed [64][32] til
 constexpr int ROWS_T = 32 * RP;     // bf16 per row-major plane tile
 constexpr int TRN_T = 64 * TPH;     // bf16 per transposed plane tile
 constexpr float QS2 = 0.125f * 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 #define CR(r, h) (((r) & 3) + 8 * ((r) >> 2) + 4 * (h))
 #define MB(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 // x y accumulated from six products (small terms first): x2y0 + x0y2 + x1y1 + x1y0 + x0y1 + x0y0
@@ -85,13 +81,6 @@ __device__ __forceinline__ bf16x8 frag_trn(const __bf16* tile, int row, int jj, 
   const bf16x4 a = *reinterpret_cast<const bf16x4*>(tile + row * TPH + 16 * jj + 4 * h);
   const bf16x4 b = *reinterpret_cast<const bf16x4*>(tile + row * TPH + 16 * jj + 8 + 4 * h);
   return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ void split8(const f32x16& s, int jj, float mul, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float x = s[8 * jj + i] * mul;
-    SPLIT1(x, i);
-  }
 }
 }  // namespace
 
@@ -170,154 +159,14 @@ __global__ __launch_bounds__(256) void emu_attn_convert_kernel(const float* __re
 }
 
 // ============================================================================================================================
-// forward: block = 128 queries (lane = query), streams 32-key tiles of K rows (3 planes) and V^T (3 planes)
-// ============================================================================================================================
-__global__ __launch_bounds__(256, 2) void emu_attn_fwd_kernel(EmuAttn a) {
-  constexpr int BUF = 3 * ROWS_T + 3 * TRN_T;
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * BUF];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = lane >> 5, c = lane & 31;
-  int qtile, bh;
-  if (!emu_block((a.Lq + 127) / 128, a.B * a.H, qtile, bh)) return;
-  const int b = bh / a.H, head = bh - b * a.H;
-  const int qrow = qtile * 128 + wave * 32 + c;
-  const __bf16* kp[3] = {a.k[0] + (size_t)bh * a.Lkp * D, a.k[1] + (size_t)bh * a.Lkp * D, a.k[2] + (size_t)bh * a.Lkp * D};
-  const __bf16* vp[3] = {a.vt[0] + (size_t)bh * D * a.Lkp, a.vt[1] + (size_t)bh * D * a.Lkp, a.vt[2] + (size_t)bh * D * a.Lkp};
-
-  bf16x8 qf[4][3];                        // Q^T fragments: k-step j <-> d = 16 j + 8 h .. + 7 of the lane's query
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const __bf16* s = a.q[p] + ((size_t)bh * a.Lqp + qrow) * D;       // qrow < Lqp always (padded with zero rows)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) qf[j][p] = *reinterpret_cast<const bf16x8*>(s + 16 * j + 8 * h);
-  }
-  const uint32_t rowkey = drop_rowkey(a.seed, (uint32_t)(bh * a.Lq + qrow));
-  float m = -INFINITY, lsum = 0.f;
-  f32x16 o[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-
-  const int ntiles = (a.kv_len + 31) / 32;
-  u32x4 r0, r1, r2, r3, r4, r5;
-#define FWD_LOAD(kt)                                   \
-  do {                                                 \
-    r0 = ld_rows(kp[0], (size_t)(kt) * 32, tid);       \
-    r1 = ld_rows(kp[1], (size_t)(kt) * 32, tid);       \
-    r2 = ld_rows(kp[2], (size_t)(kt) * 32, tid);       \
-    r3 = ld_trn(vp[0], a.Lkp, (size_t)(kt) * 32, tid); \
-    r4 = ld_trn(vp[1], a.Lkp, (size_t)(kt) * 32, tid); \
-    r5 = ld_trn(vp[2], a.Lkp, (size_t)(kt) * 32, tid); \
-  } while (0)
-#define FWD_STORE(buf)                                 \
-  do {                                                 \
-    st_rows((buf), r0, tid);                           \
-    st_rows((buf) + ROWS_T, r1, tid);                  \
-    st_rows((buf) + 2 * ROWS_T, r2, tid);              \
-    st_trn((buf) + 3 * ROWS_T, r3, tid);               \
-    st_trn((buf) + 3 * ROWS_T + TRN_T, r4, tid);       \
-    st_trn((buf) + 3 * ROWS_T + 2 * TRN_T, r5, tid);   \
-  } while (0)
-  FWD_LOAD(0);
-  FWD_STORE(lds);
-  __syncthreads();
-  for (int kt = 0; kt < ntiles; ++kt) {
-    const int cur = kt & 1;
-    FWD_LOAD(min(kt + 1, ntiles - 1));              // unconditional (past the end the last tile is re-read and dropped)
-    const __bf16* K0 = lds + cur * BUF;
-    const __bf16* V0 = K0 + 3 * ROWS_T;
-    f32x16 s;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(&K0[c * RP + 16 * j + 8 * h]);
-      const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(&K0[ROWS_T + c * RP + 16 * j + 8 * h]);
-      const bf16x8 k2 = *reinterpret_cast<const bf16x8*>(&K0[2 * ROWS_T + c * RP + 16 * j + 8 * h]);
-      MB6(s, k0, k1, k2, qf[j][0], qf[j][1], qf[j][2]);
-    }
-    if (kt == ntiles - 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (kt * 32 + CR(r, h) >= a.kv_len) s[r] = -INFINITY;
-    }
-    float mt = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[r]);
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    // lazy rescale: the running reference m only moves when some query of the wave sees a score more than 2^8 above it (always
-    // on the first tile, almost never afterwards) - exp2(s - m) <= 256 stays exact through the three-way split, O / l and the LSE
-    // m + log2(l) are unchanged by the choice of reference, and the 32 multiplies of the accumulator are skipped
-    if (__any(mt > m + 8.f)) {
-      const float mn = fmaxf(m, mt);
-      const float alpha = __builtin_amdgcn_exp2f(m - mn);
-      lsum *= alpha;
-      m = mn;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-    }
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float p = __builtin_amdgcn_exp2f(s[r] - m);
-      ps += p;
-      s[r] = p;
-    }
-    lsum += ps;
-    if (a.drop_p > 0.f) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] *= drop_scale(rowkey, (uint32_t)(kt * 32 + CR(r, h)), a.thresh, a.inv_keep);
-    }
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      bf16x8 p0, p1, p2;
-      split8(s, jj, 1.f, p0, p1, p2);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 v0 = frag_trn(V0, dt * 32 + c, jj, h);
-        const bf16x8 v1 = frag_trn(V0 + TRN_T, dt * 32 + c, jj, h);
-        const bf16x8 v2 = frag_trn(V0 + 2 * TRN_T, dt * 32 + c, jj, h);
-        MB6(o[dt], v0, v1, v2, p0, p1, p2);
-      }
-    }
-    if (kt + 1 < ntiles) FWD_STORE(lds + (cur ^ 1) * BUF);
-    __syncthreads();
-  }
-#undef FWD_LOAD
-#undef FWD_STORE
-  const float ltot = lsum + __shfl_xor(lsum, 32, 64);
-  uint32_t omax = 0u;
-  if (qrow < a.Lq) {
-    const float inv = 1.f / ltot;
-    float* op = a.out + ((size_t)b * a.Lq + qrow) * a.ldo + head * D;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 ov = make_float4(o[t][4 * g + 0] * inv, o[t][4 * g + 1] * inv, o[t][4 * g + 2] * inv, o[t][4 * g + 3] * inv);
-        *reinterpret_cast<float4*>(op + 32 * t + 8 * g + 4 * h) = ov;
-        omax = max(omax, mag_bits4(ov));
-      }
-    if (h == 0 && a.lse) a.lse[(size_t)bh * a.Lq + qrow] = m + log2f(ltot);       // log2 domain
-  }
-  if (a.mag) {                               // row magnitudes of o (common.h): lanes c, c + 32 hold the two halves of the row's head slice
-    omax = max(omax, (uint32_t)__shfl_xor((int)omax, 32, 64));
-    if (h == 0 && qrow < a.Lq) atomicMax(a.mag + (size_t)b * a.Lq + qrow, omax);
-  }
-}
-
-
-// ============================================================================================================================
-// forward, second form (round 4): the same tiles, fragments, product order and online softmax as emu_attn_fwd_kernel (with
-// dropout off the outputs are bit identical), software-pipelined over the key tiles and hand-interleaved:
+// forward: block = 128 queries (lane = query), streams 32-key tiles of K rows and V^T (3 planes each; NPL below), online softmax,
+// software-pipelined over the key tiles and hand-interleaved:
 //     S phase : the 24 MFMAs of S(t + 1) = K(t + 1) . Q^T   with the softmax / dropout / three-way split of tile t behind them
 //     PV phase: the 24 MFMAs of O^T += V(t)^T . P(t)^T      with the running maximum of tile t + 1, its dropout decisions (one hash
 //               per two keys), the staging writes of K(t + 2) / V(t + 1) and the loads of K(t + 3) / V(t + 2) behind them
-// In the first form a wave runs [24 MFMAs | ~250 VALU | 24 MFMAs] per key tile and the MFMA pipe is 40 % busy (PMC, round 4): the
-// VALU work of a tile is about as long as its MFMAs, and on this part it only hides under the SAME wave's MFMAs.  Here every unit
+// Left to the compiler a wave runs [24 MFMAs | ~250 VALU | 24 MFMAs] per key tile and the MFMA pipe is 40 % busy (PMC, round 4, the
+// retired unpipelined kernel: profiles/r04_pmc_attention_counters.txt): the VALU work of a tile is about as long as its MFMAs,
+// and on this part it only hides under the SAME wave's MFMAs.  Here every unit
 // of it is pinned behind one MFMA of the other tile (tools/gen/attn_fwd2_phase.py).  K rows and V^T tiles are double-buffered
 // separately (K(t + 1) and V(t) are read while K(t + 2) and V(t + 1) are written): four __shared__ objects of 13.5 KB, one barrier
 // per tile.
@@ -550,7 +399,10 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
   }
   uint32_t hbase = rowkey + (uint32_t)(2 * h) * 0x9E3779B9U;      // + (kt * 16) * G per tile: the hash input of the lane's key pair 0 (keys 4 h, 4 h + 1)
   // the statistics step every tile goes through once its scores exist (s_nxt = scores of tile `KT`): mask the keys past kv_len,
-  // running maximum with the lazy rescale of the first form, dropout decisions (prologue only: the loop does them in units)
+  // running maximum with a lazy rescale, dropout decisions (prologue only: the loop does them in units).  Lazy rescale: the running
+  // reference m only moves when some query of the wave sees a score more than 2^8 above it (always on the first tile, almost never
+  // afterwards) - exp2(s - m) <= 256 stays exact through the split, O / l and the LSE m + log2(l) are unchanged by the choice of
+  // reference, and the 32 multiplies of the accumulator are skipped
 #define FWD2_TILE_STATS(KT, DO_HASH)                                                                                   \
   do {                                                                                                                 \
     if ((KT) == lastt) {                                                                                               \
@@ -648,308 +500,6 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
   }
 }
 #pragma pop_macro("MB")
-
-
-namespace {
-// element offset (bf16) of the 16-byte chunk `ch` of row `r` of a [rows][128] tile (256-byte rows, 16 chunks)
-__device__ __forceinline__ int b2_wide_off(int r, int ch) { return r * 128 + ((ch ^ (r & 15)) << 3); }
-#define MF16(a_, b_, c_) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a_), (b_), (c_), 0, 0, 0)
-#define MF6(acc, x0, x1, x2, y0, y1, y2) \
-  do {                                   \
-    acc = MF16(x2, y0, acc);             \
-    acc = MF16(x0, y2, acc);             \
-    acc = MF16(x1, y1, acc);             \
-    acc = MF16(x1, y0, acc);             \
-    acc = MF16(x0, y1, acc);             \
-    acc = MF16(x0, y0, acc);             \
-  } while (0)
-}  // namespace
-
-// ============================================================================================================================
-// backward, fused dK / dV / dQ in one pass (5 GEMM-equivalents).  Block = 128 keys, 8 waves, wave = 16 keys (lane l: key l % 16,
-// k-group g = l / 16), every contraction on v_mfma_f32_16x16x32_bf16 - 16-wide tiles keep the per-lane state (K, V fragments 48
-// registers, dK, dV accumulators 32) under 256 registers, so two waves share a SIMD (a first form with 32 keys per wave on
-// 32x32x16 tiles needed > 400 registers, ran one wave per SIMD and took 3.4 ms where this one takes 2.2 ms at B = 32, S = 2048):
-//   S, dP      [32 q x 16 keys] = two 16 x 16 tiles, A = Q / dO rows from LDS, B = the lane's K / V fragments (registers)
-//   dV^T, dK^T [64 d x 16 keys] = four tiles each, A = dO^T / Q^T fragments, B = Pd / dS straight from the S / dP accumulator
-//              registers (a lane holds q = 16 qh + 4 g + i: k-slot 8 g + i <-> q = 4 g + i, 8 g + 4 + i <-> q = 16 + 4 g + i)
-//   dQ         [32 q x 64 d]    = eight 16 x 16 tiles, one per wave, A = the dS tile T (LDS, written by all waves), B = K^T fragments
-// The two waves of a SIMD do not run the same phase at the same time: waves 0-3 ("early") and 4-7 ("late", one half-step behind;
-// wave w and w + 4 share a SIMD) alternate two half-steps, separated by workgroup barriers (a lock-step variant of the same
-// kernel - all eight waves in phase, transposed operand tiles staged separately - measured 2.36 ms against 2.29):
-//     X(t): S / dP of query tile t  +  dQ of tile t - 2 (early) or t - 1 (late)          [MFMA only]
-//     Y(t): softmax / splits of tile t (dS -> T[t & 1])  ->  dV / dK of tile t           [VALU, then MFMA]
-// so that in every half-step one wave of each SIMD issues MFMAs while the other runs its VALU phase.  That needs tile t + 1 staged
-// while tile t is still being read and dS tiles of two query tiles alive: both double-buffered - which fits 160 KB only because
-// the TRANSPOSED operand fragments (dO^T / Q^T for dV / dK, K^T for dQ) are no longer staged as separate tiles but read from the
-// row-major tiles with ds_read_b64_tr_b16 (within 16 lanes: lane 4 r + c supplies the address of columns 4 c .. 4 c + 3 of row r,
-// lane j receives [row0[j], row1[j], row2[j], row3[j]] - measured, tools/ubench/ds_tr_probe.hip).  LDS: Q / dO row tiles 2 x 24 KB,
-// T 2 x 24 KB, the block's K rows 48 KB.  The early waves' 256 threads stage everything.
-// ============================================================================================================================
-namespace {
-constexpr int B3_ROWS = 32 * 64;                 // bf16 per plane tile [32 q][64 d]
-constexpr int B3_ST = 6 * B3_ROWS;               // one staging buffer: Q planes 0-2, dO planes 0-2
-constexpr int B3_T = 32 * 128;                   // bf16 per dS plane [32 q][128 keys]
-constexpr int B3_TB = 3 * B3_T;
-constexpr int B3_KS = 128 * 64;                  // bf16 per K plane [128 keys][64 d]
-constexpr int B3_TS0 = 2 * B3_ST, B3_KS0 = B3_TS0 + 2 * B3_TB, B3_BF16 = B3_KS0 + 3 * B3_KS;
-constexpr unsigned B3_LDS_BYTES = B3_BF16 * 2u + 2u * 64u * 4u;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-// 16-byte chunk `ch` of row `r`.  Row tiles: chunk ^ (r & 6) serves both the 16-byte reads of S / dP (lane groups mix rows 0-3 /
-// 12-15 at one chunk with rows 4-11 at the next) and the transpose reads (32 lanes = 8 consecutive rows x 32 bytes: rows of equal
-// parity share their banks and must land in different chunk pairs).  K rows: the transpose reads of dQ take rows {0-3, 8-11} /
-// {4-7, 12-15} of every 16 together, so bits 1 and 3 of the row select the chunk pair.
-__device__ __forceinline__ int b3_rows_off(int r, int ch) { return r * 64 + ((ch ^ (r & 6)) << 3); }
-__device__ __forceinline__ int b3_ks_off(int r, int ch) { return r * 64 + ((ch ^ ((((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2))) << 3); }
-__device__ __forceinline__ bf16x8 b3_tr8(const __bf16* lo, const __bf16* hi) {
-  const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(lo));
-  const s16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(hi));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-}  // namespace
-
-template <bool DROP>
-__global__ __launch_bounds__(512, 1) void emu_attn_bwd_stag_kernel(EmuAttn a) {
-  extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
-  float* stats = reinterpret_cast<float*>(lds + B3_BF16);       // [2][lse 32 (log2 domain) | delta 32]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l16 = lane & 15, g = lane >> 4;
-  int ktile, bh;
-  const int nkb = (a.Lk + 127) / 128;
-  if (!emu_block(nkb, a.B * a.H, ktile, bh)) return;
-  const int b = bh / a.H, head = bh - b * a.H;
-  const int key = ktile * 128 + wave * 16 + l16;
-  const bool kvalid = key < a.kv_len;
-  const int nq = ktile * 128 < a.kv_len ? (a.Lq + 31) / 32 : 0;
-  const bool early = wave < 4;
-  const int lag = early ? 0 : 1;
-
-  // resident B operands of S / dP: this lane's key, d = 32 ks + 8 g .. + 7
-  bf16x8 kf[2][3], vf[2][3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const size_t ro = ((size_t)bh * a.Lkp + key) * D;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      kf[ks][p] = *reinterpret_cast<const bf16x8*>(a.k[p] + ro + 32 * ks + 8 * g);
-      vf[ks][p] = *reinterpret_cast<const bf16x8*>(a.v[p] + ro + 32 * ks + 8 * g);
-    }
-  }
-  // the block's K rows: 3 planes x [128 keys][64 d] = 3 x 1024 chunks, two per thread and plane
-  if (nq > 0) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int id = tid + 512 * i, r = id >> 3, ch = id & 7;
-        *reinterpret_cast<u32x4*>(lds + B3_KS0 + p * B3_KS + b3_ks_off(r, ch)) =
-            *reinterpret_cast<const u32x4*>(a.k[p] + ((size_t)bh * a.Lkp + ktile * 128 + r) * D + ch * 8);
-      }
-  }
-  f32x4 dk[4], dv[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) { dk[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-  // staging (early waves only: thread -> row tid >> 3, chunk tid & 7 of each of the six plane tiles), running pointers
-  const int tt = tid & 255;
-  u32x4 sg[6];
-  float rl = INFINITY, re = 0.f;
-  // (uniform plane bases + one 32-bit element offset per thread: the loads take the scalar-base form, no 64-bit pointers in VGPRs)
-  const size_t rowbase = (size_t)bh * a.Lqp * D;
-  const __bf16* qb0 = a.q[0] + rowbase; const __bf16* qb1 = a.q[1] + rowbase; const __bf16* qb2 = a.q[2] + rowbase;
-  const __bf16* db0 = a.d[0] + rowbase; const __bf16* db1 = a.d[1] + rowbase; const __bf16* db2 = a.d[2] + rowbase;
-  unsigned goff = (unsigned)((tt >> 3) * D + (tt & 7) * 8);      // < 2^31 elements per (b, head): Lqp * 64
-  const int st_o = b3_rows_off(tt >> 3, tt & 7);
-#define B3_LOAD(QTI_)                                                                                                  \
-  do {                                                                                                                 \
-    sg[0] = *reinterpret_cast<const u32x4*>(qb0 + goff); sg[1] = *reinterpret_cast<const u32x4*>(qb1 + goff);          \
-    sg[2] = *reinterpret_cast<const u32x4*>(qb2 + goff); sg[3] = *reinterpret_cast<const u32x4*>(db0 + goff);          \
-    sg[4] = *reinterpret_cast<const u32x4*>(db1 + goff); sg[5] = *reinterpret_cast<const u32x4*>(db2 + goff);          \
-    if (tid < 32) {                                                                                                    \
-      const int q_ = (QTI_) * 32 + tid;                                                                                \
-      rl = q_ < a.Lq ? a.lse_in[(size_t)bh * a.Lq + q_] : INFINITY;                                                    \
-      re = q_ < a.Lq ? a.delta[(size_t)bh * a.Lq + q_] : 0.f;                                                          \
-    }                                                                                                                  \
-  } while (0)
-#define B3_ADVANCE() do { goff += 32 * D; } while (0)
-#define B3_STAGE(BUF_)                                                                                                 \
-  do {                                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < 6; ++i)                                                                      \
-      *reinterpret_cast<u32x4*>(lds + (BUF_) * B3_ST + i * B3_ROWS + st_o) = sg[i];                                    \
-    if (tid < 32) { stats[(BUF_) * 64 + tid] = rl; stats[(BUF_) * 64 + 32 + tid] = re; }                              \
-  } while (0)
-  float* part = a.dq_part + ((size_t)ktile * a.B * a.H + bh) * a.Lq * D;
-  const int qh_o = wave >> 2, dt_o = wave & 3;          // this wave's dQ output tile
-  // where this lane's dS values go in a T buffer: row q = 16 qh + 4 g + i, key column 16 wave + l16 (swizzled chunk)
-  int tw[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) tw[i] = (4 * g + i) * 128 + ((((2 * wave + (l16 >> 3)) ^ (4 * g)) ^ i) << 3) + (l16 & 7);
-  // transpose-read addresses: row 4 g + (l16 >> 2) (+ 16), columns 4 (l16 & 3) .. + 3 of a 16-column block
-  const int trq = 4 * g + (l16 >> 2), trc = l16 & 3;
-  if (nq > 0 && early) {
-    B3_LOAD(0);
-    B3_STAGE(0);
-    if (nq > 1) B3_ADVANCE();
-    B3_LOAD(min(1, nq - 1));
-  }
-  __syncthreads();                         // tile 0 and the K rows are in LDS
-  f32x4 s[2], dp[2];
-#pragma unroll
-  for (int qh = 0; qh < 2; ++qh) { s[qh] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[qh] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  bf16x8 p0, p1, p2, g0, g1, g2;           // Pd and dS of the lane's 8 (query, key) pairs as bf16 triples: element 4 qh + i
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { p0[e] = p1[e] = p2[e] = g0[e] = g1[e] = g2[e] = (__bf16)0.f; }
-  // softmax / dropout / dS algebra + the two exact three-way splits for the four queries 16 QH + 4 g + i of tile T_ (statistics in ST_)
-#define B3_SOFTMAX(QH, T_, ST_)                                                                                        \
-  do {                                                                                                                 \
-    const f32x4 lsq = *reinterpret_cast<const f32x4*>((ST_) + 16 * (QH) + 4 * g);                                      \
-    const f32x4 esq = *reinterpret_cast<const f32x4*>((ST_) + 32 + 16 * (QH) + 4 * g);                                 \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                    \
-      const int qi = 16 * (QH) + 4 * g + i, e = 4 * (QH) + i;                                                          \
-      const float pe = __builtin_amdgcn_exp2f(s[QH][i] - lsq[i]);                                                      \
-      const float pr = kvalid ? pe : 0.f;                                                                              \
-      float dsc = 1.f;                                                                                                 \
-      if (DROP)                                                                                                        \
-        dsc = drop_scale(drop_rowkey(a.seed, (uint32_t)(bh * a.Lq + (T_) * 32) + (uint32_t)qi), (uint32_t)key, a.thresh, a.inv_keep); \
-      const float pd = pr * dsc;                                                                                       \
-      const float ds = pr * (dp[QH][i] * dsc - esq[i]);                                                                \
-      {                                                                                                                \
-        const __bf16 a_ = (__bf16)pd; const float r1_ = pd - (float)a_; const __bf16 b_ = (__bf16)r1_; const float r2_ = r1_ - (float)b_; \
-        p0[e] = a_; p1[e] = b_; p2[e] = (__bf16)r2_;                                                                   \
-      }                                                                                                                \
-      {                                                                                                                \
-        const __bf16 a_ = (__bf16)ds; const float r1_ = ds - (float)a_; const __bf16 b_ = (__bf16)r1_; const float r2_ = r1_ - (float)b_; \
-        g0[e] = a_; g1[e] = b_; g2[e] = (__bf16)r2_;                                                                   \
-      }                                                                                                                \
-    }                                                                                                                  \
-  } while (0)
-  const int nhalf = nq > 0 ? 2 * nq + 3 : 0;
-  for (int hs = 0; hs < nhalf; ++hs) {
-    const int kk = hs - lag;
-    if (kk >= 0) {
-      const int t = kk >> 1;
-      if (!(kk & 1)) {
-        // ---------------- X(t): S / dP of tile t, dQ of an older tile -------------------------------------------------------
-        if (t < nq) {
-          const __bf16* ST = lds + (t & 1) * B3_ST;
-          // (the six products of BOTH k-steps in order of magnitude - x2 y0, x0 y2, x1 y1 | x1 y0, x0 y1 | x0 y0)
-#define B3_SDP(acc, TILE, BF)                                                                                          \
-  do {                                                                                                                 \
-    const int o0_ = b3_rows_off(16 * qh + l16, g), o1_ = b3_rows_off(16 * qh + l16, 4 + g);                             \
-    const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + o0_);                                             \
-    const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + B3_ROWS + o0_);                                   \
-    const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + 2 * B3_ROWS + o0_);                               \
-    const bf16x8 c0 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + o1_);                                             \
-    const bf16x8 c1 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + B3_ROWS + o1_);                                   \
-    const bf16x8 c2 = *reinterpret_cast<const bf16x8*>(ST + (TILE) + 2 * B3_ROWS + o1_);                               \
-    f32x4 t_ = {0.f, 0.f, 0.f, 0.f};                                                                                   \
-    t_ = MF16(a2, BF[0][0], t_); t_ = MF16(c2, BF[1][0], t_);                                                           \
-    t_ = MF16(a0, BF[0][2], t_); t_ = MF16(c0, BF[1][2], t_);                                                           \
-    t_ = MF16(a1, BF[0][1], t_); t_ = MF16(c1, BF[1][1], t_);                                                           \
-    t_ = MF16(a1, BF[0][0], t_); t_ = MF16(c1, BF[1][0], t_);                                                           \
-    t_ = MF16(a0, BF[0][1], t_); t_ = MF16(c0, BF[1][1], t_);                                                           \
-    t_ = MF16(a0, BF[0][0], t_); t_ = MF16(c0, BF[1][0], t_);                                                           \
-    acc = t_;                                                                                                          \
-  } while (0)
-#pragma unroll
-          for (int qh = 0; qh < 2; ++qh) {
-            B3_SDP(s[qh], 0, kf);
-            B3_SDP(dp[qh], 3 * B3_ROWS, vf);
-          }
-#undef B3_SDP
-          // the first half of the tile's VALU work already here, under this wave's own remaining MFMAs (the other half and the
-          // T stores follow in Y): balances the two half-steps
-          B3_SOFTMAX(0, t, stats + (t & 1) * 64);
-        }
-        const int td = t - 2 + lag;
-        if (td >= 0 && td < nq) {
-          // dQ tile of this wave for query tile td: rows 16 qh_o .., columns 16 dt_o ..: sum over the block's 128 keys
-          const __bf16* TS = lds + B3_TS0 + (td & 1) * B3_TB;
-          const __bf16* KS = lds + B3_KS0;
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f}, mid = {0.f, 0.f, 0.f, 0.f}, big = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const int ot = b2_wide_off(16 * qh_o + l16, 4 * ks + g);
-            const int r0 = 32 * ks + 8 * g + (l16 >> 2);
-            const int k0 = b3_ks_off(r0, 2 * dt_o + (trc >> 1)) + (trc & 1) * 4, k1 = b3_ks_off(r0 + 4, 2 * dt_o + (trc >> 1)) + (trc & 1) * 4;
-            const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(TS + ot);
-            const bf16x8 x1 = *reinterpret_cast<const bf16x8*>(TS + B3_T + ot);
-            const bf16x8 x2 = *reinterpret_cast<const bf16x8*>(TS + 2 * B3_T + ot);
-            const bf16x8 y0 = b3_tr8(KS + k0, KS + k1);
-            const bf16x8 y1 = b3_tr8(KS + B3_KS + k0, KS + B3_KS + k1);
-            const bf16x8 y2 = b3_tr8(KS + 2 * B3_KS + k0, KS + 2 * B3_KS + k1);
-            acc = MF16(x2, y0, acc); acc = MF16(x0, y2, acc); acc = MF16(x1, y1, acc);
-            mid = MF16(x1, y0, mid); mid = MF16(x0, y1, mid);
-            big = MF16(x0, y0, big);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int q = td * 32 + 16 * qh_o + 4 * g + i;
-            if (q < a.Lq) part[(size_t)q * D + 16 * dt_o + l16] = (acc[i] + mid[i]) + big[i];
-          }
-        }
-      } else {
-        // ---------------- Y(t): stage tile t + 1 (early), softmax of tile t, dV / dK of tile t ---------------------------------
-        if (early && t + 1 < nq) {
-          B3_STAGE((t + 1) & 1);
-          if (t + 2 < nq) B3_ADVANCE();
-          B3_LOAD(min(t + 2, nq - 1));
-        }
-        if (t < nq) {
-          B3_SOFTMAX(1, t, stats + (t & 1) * 64);
-          __bf16* TW = lds + B3_TS0 + (t & 1) * B3_TB;
-#pragma unroll
-          for (int qh = 0; qh < 2; ++qh)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              __bf16* tp = TW + tw[i] + qh * (16 * 128);
-              tp[0] = g0[4 * qh + i]; tp[B3_T] = g1[4 * qh + i]; tp[2 * B3_T] = g2[4 * qh + i];
-            }
-          // dV^T[d][key] += dO^T[d][q] . Pd[q][key] ;  dK^T[d][key] += Qs^T[d][q] . dS[q][key]: the transposed fragments come out
-          // of the row tiles through the transpose read (k-slots 8 g + i <-> q = 4 g + i, 8 g + 4 + i <-> q = 16 + 4 g + i)
-          const __bf16* ST = lds + (t & 1) * B3_ST;
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            const int o0 = b3_rows_off(trq, 2 * dt + (trc >> 1)) + (trc & 1) * 4, o1 = b3_rows_off(trq + 16, 2 * dt + (trc >> 1)) + (trc & 1) * 4;
-            const bf16x8 t0 = b3_tr8(ST + o0, ST + o1);
-            const bf16x8 t1 = b3_tr8(ST + B3_ROWS + o0, ST + B3_ROWS + o1);
-            const bf16x8 t2 = b3_tr8(ST + 2 * B3_ROWS + o0, ST + 2 * B3_ROWS + o1);
-            const bf16x8 o0_ = b3_tr8(ST + 3 * B3_ROWS + o0, ST + 3 * B3_ROWS + o1);
-            const bf16x8 o1_ = b3_tr8(ST + 4 * B3_ROWS + o0, ST + 4 * B3_ROWS + o1);
-            const bf16x8 o2_ = b3_tr8(ST + 5 * B3_ROWS + o0, ST + 5 * B3_ROWS + o1);
-            MF6(dv[dt], o0_, o1_, o2_, p0, p1, p2);
-            MF6(dk[dt], t0, t1, t2, g0, g1, g2);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-#undef B3_LOAD
-#undef B3_ADVANCE
-#undef B3_STAGE
-#undef B3_SOFTMAX
-  uint32_t gmax = 0u;
-  if (key < a.Lk) {
-    float* pk = a.dk + ((size_t)b * a.Lk + key) * a.ldk + head * D;
-    float* pv = a.dv + ((size_t)b * a.Lk + key) * a.ldv + head * D;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      // Q was pre-scaled by log2(e)/8: dK = dS^T.Q / 8 = (dS^T.Qs) * ln 2
-      const float4 gk = make_float4(dk[dt][0] * LN2, dk[dt][1] * LN2, dk[dt][2] * LN2, dk[dt][3] * LN2);
-      const float4 gv = make_float4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
-      *reinterpret_cast<float4*>(pk + 16 * dt + 4 * g) = gk;
-      *reinterpret_cast<float4*>(pv + 16 * dt + 4 * g) = gv;
-      gmax = max(gmax, max(mag_bits4(gk), mag_bits4(gv)));
-    }
-  }
-  if (a.mag) {                               // row magnitudes of [dq | dk | dv] (common.h): the four k-groups of a key hold its row
-    gmax = max(gmax, (uint32_t)__shfl_xor((int)gmax, 16, 64));
-    gmax = max(gmax, (uint32_t)__shfl_xor((int)gmax, 32, 64));
-    if (g == 0 && key < a.Lk) atomicMax(a.mag + (size_t)b * a.Lk + key, gmax);
-  }
-}
 
 // delta[bh][q] = sum_d dO[q][d] * O[q][d]  (f32; 16 lanes per (q, head))
 __global__ __launch_bounds__(256) void emu_attn_delta_kernel(const float* __restrict__ o, int ldo, const float* __restrict__ dout,
@@ -1071,16 +621,13 @@ int fwd_over_planes(float* o, int ldo, float* lse, int B, int H, int Lq, int Lk,
   a.out = o; a.lse = lse; a.ldo = ldo; a.mag = o_mag; a.q_hm = q_hm; a.k_hm = k_hm; a.v_hm = v_hm;
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.kv_len = kv_len;
   a.drop_p = drop_p; a.inv_keep = 1.f / (1.f - drop_p); a.thresh = drop_threshold(drop_p); a.seed = seed;
-  static int form = -1;                       // HOISDF_EMU_ATTN_FWD=1: the first (unpipelined) form (A/B runs)
-  if (form < 0) { const char* e = getenv("HOISDF_EMU_ATTN_FWD"); form = (e && atoi(e) == 1) ? 1 : 2; }
   const dim3 fgrid(cdiv(Lq, 128) * 8 * cdiv(B * H, 8));
   if (q_hm) {
     // (P is carried as 2^6 P up to 2^14 and the keep factor 1 / (1 - p) goes in before the f16 split: p < 0.75 keeps it below 65504)
     HOISDF_REQUIRE(drop_p < 0.75f, HOISDF_ERR_INVALID, "attention_fwd_emu (f16x2 form): drop_p = %f, must be below 0.75", drop_p);
     if (drop_p > 0.f) hipLaunchKernelGGL((emu_attn_fwd2_kernel<true, 2, true>), fgrid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((emu_attn_fwd2_kernel<false, 2, true>), fgrid, dim3(256), 0, st, a);
-  } else if (form == 1) hipLaunchKernelGGL(emu_attn_fwd_kernel, fgrid, dim3(256), 0, st, a);
-  else if (drop_p > 0.f) hipLaunchKernelGGL((emu_attn_fwd2_kernel<true, 3, false>), fgrid, dim3(256), 0, st, a);
+  } else if (drop_p > 0.f) hipLaunchKernelGGL((emu_attn_fwd2_kernel<true, 3, false>), fgrid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((emu_attn_fwd2_kernel<false, 3, false>), fgrid, dim3(256), 0, st, a);
   return check_launch("attention_fwd_emu");
 }
@@ -1239,17 +786,6 @@ int hoisdf::attention_bwd_emu_mag(const float* q, int ldq, const float* k, int l
                  HOISDF_ERR_INVALID, "attention_bwd_emu: bad leading dims / alignment");
   const long need = hoisdf_attention_bwd_emu_workspace(B, H, Lq, Lk, fwd_workspace ? 1 : 0);
   HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_WORKSPACE, "attention_bwd_emu: workspace %ld < %ld bytes", workspace_bytes, need);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(emu_attn_bwd_stag_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)B3_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(emu_attn_bwd_stag_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)B3_LDS_BYTES) != hipSuccess) {
-      set_error("attention_bwd_emu: cannot raise the dynamic LDS limit to %u bytes", B3_LDS_BYTES);
-      return HOISDF_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
   const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
   hipStream_t st = as_stream(stream);
   const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
@@ -1287,44 +823,7 @@ int hoisdf::attention_bwd_emu_mag(const float* q, int ldq, const float* k, int l
                        B, H, Lq, g_mag, (const float*)a.dq_scale);
     return check_launch("attention_bwd_emu dq reduce");
   }
-  // HOISDF_EMU_ATTN_BWD: (default) the round-5 kernel with dQ summed across the key blocks through an ordered running sum in L2;
-  // "4p": the same kernel with the per-key-block partial buffer + reduce pass; "3": the round-3 kernel (8 waves x 16 keys) - A/B runs
-  static int form = -1;
-  if (form < 0) { const char* e = getenv("HOISDF_EMU_ATTN_BWD"); form = !e ? 5 : (atoi(e) == 3 ? 3 : (e[0] == '4' && e[1] == 'p' ? 4 : 5)); }
-  if (form == 5) {
-    // HOISDF_EMU_ATTN_BWD_CHAIN=G (default 1 = one partial per key block + the reduce pass): chains of G key blocks add their dQ
-    // contributions to ONE running sum in order, through the XCD's L2.  An EXPERIMENT, off by default: G = 16 takes the launch from
-    // 1.61 to ~0.6 GB of HBM traffic with bit-identical results, at the SAME speed (2.150 vs 2.155 ms per call at B = 32, S = 2048;
-    // G = 4: 2.18, G = 2: 2.23, and slower at 512 queries: 0.83 vs 0.74) - the partial traffic was never what bounds this kernel (the
-    // board sits at its 1400 W cap, HBM at 0.8 TB/s) and the waits of the chain eat what the reduce pass cost.  It is also only
-    // correct while all key blocks of a (b, head) run on one XCD (observed dispatch behaviour, not a HIP guarantee).
-    static int G = -1;
-    if (G < 0) { const char* e = getenv("HOISDF_EMU_ATTN_BWD_CHAIN"); G = e ? atoi(e) : 1; if (G < 1) G = 1; }
-    const int nkb = cdiv(Lk, 128), nlive = cdiv(kv_len, 128), ngrp = cdiv(nlive, G);
-    // the counters sit behind the ngrp running sums (the region holds nkb partial slots: always room unless G = 1)
-    int* flags = reinterpret_cast<int*>(part + (size_t)ngrp * B * H * Lq * 64);
-    const size_t flag_bytes = (size_t)B * H * nkb * 4 * sizeof(int);
-    const bool chain = G > 1 && nlive > 1 && (size_t)(nkb - ngrp) * B * H * Lq * 64 * sizeof(float) >= flag_bytes &&
-                       !g_mag;       // (a chain of all key blocks writes dq itself: nobody would fold its magnitude)
-    if (chain) {
-      a.dq = dq; a.ldq = ldq; a.dq_flags = flags; a.chain_group = G;
-      if (hipMemsetAsync(flags, 0, flag_bytes, st) != hipSuccess) { set_error("attention_bwd_emu: clearing the chain counters failed"); return HOISDF_ERR_LAUNCH; }
-      if (int rc = attention_bwd4_emu_launch(a, true, st)) return rc;
-      if (ngrp == 1) return HOISDF_OK;          // (the chain's last block wrote dq itself)
-      const long n4c = (long)B * H * Lq * 16;
-      hipLaunchKernelGGL(emu_attn_dq_reduce_kernel, dim3((unsigned)((n4c + 255) / 256)), dim3(256), 0, st, part, ngrp, dq, ldq, B, H, Lq, g_mag, (const float*)nullptr);
-      return check_launch("attention_bwd_emu dq reduce");
-    }
-    if (int rc = attention_bwd4_emu_launch(a, false, st)) return rc;
-  } else
-  if (form == 4) {
-    if (int rc = attention_bwd4_emu_launch(a, false, st)) return rc;
-  } else {
-    const dim3 grid(cdiv(Lk, 128) * 8 * cdiv(B * H, 8));
-    if (drop_p > 0.f) hipLaunchKernelGGL(emu_attn_bwd_stag_kernel<true>, grid, dim3(512), B3_LDS_BYTES, st, a);
-    else hipLaunchKernelGGL(emu_attn_bwd_stag_kernel<false>, grid, dim3(512), B3_LDS_BYTES, st, a);
-    if (int rc = check_launch("attention_bwd_emu")) return rc;
-  }
+  if (int rc = attention_bwd4_emu_launch(a, st)) return rc;
   const long n4 = (long)B * H * Lq * 16;
   hipLaunchKernelGGL(emu_attn_dq_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, cdiv(kv_len, 128), dq, ldq,
                      B, H, Lq, g_mag, (const float*)nullptr);

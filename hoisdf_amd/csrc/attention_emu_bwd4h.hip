@@ -57,17 +57,7 @@ __device__ __forceinline__ uint32_t cvt2(f32x2 v) { return __builtin_bit_cast(ui
 __device__ __forceinline__ f32x2 unpack2(uint32_t w) { return __builtin_convertvector(__builtin_bit_cast(f16x2, w), f32x2); }
 }  // namespace
 
-// CHAIN (experiment, HOISDF_EMU_ATTN_BWD_CHAIN=G, off by default): fewer dQ partials.  The key blocks of a (b, head) run side by side
-// on ONE XCD (emu_block) and walk the query tiles at the same pace; within a chain of G consecutive key blocks, block kb adds its
-// contribution of a query tile to a running sum that block kb - 1 has already added to - wave w of block kb waits for wave w of block
-// kb - 1 through a counter in L2 (same XCD: plain stores + sc1 loads, no fences), reads the 8 rows x 64 d it owns, adds, writes.
-// Fixed order = run-to-run identical, and with G = 16 bit-identical to the reduce pass (same association).  Measured (B = 32,
-// S = 2048, whole call): G = 16 2.150 ms, G = 8 2.16, G = 4 2.18, G = 2 2.23, partials + reduce 2.155: the 1.07 GB of partial traffic
-// is not what bounds the kernel, and a chain costs its members a start-up skew (one L2 round trip per stage, idle time with one
-// workgroup per CU).  Kept as the measured answer to "halve the dQ partials" (profiles/r05_attn_bwd_dq_chain_ab.txt); correctness
-// relies on the observed block -> XCD placement, which HIP does not promise - hence not the default.
-// (Blocks wait on LOWER block indices only, which the dispatcher starts first; the wait is bounded all the same.)
-template <bool DROP, bool CHAIN>
+template <bool DROP>
 __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
   extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
   float* const xbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + X0_BYTES);
@@ -185,15 +175,7 @@ __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
 #define B4_STOREP(i_, BUF_) do { *reinterpret_cast<u32x4*>(lds + (BUF_) + (i_) * QD_PLANE + st_o) = sg[i_]; } while (0)
 #define B4_STORES(SB_) do { if (tid < 64) stats[(SB_) + tid] = rstat; } while (0)
 
-  // CHAIN: key blocks [G grp, G grp + G) of a (b, head) form one chain; its running sum is partial number grp
-  const int nkb_live = (a.kv_len + 127) / 128;                  // key blocks that take part (the others have nq = 0)
-  const int G = CHAIN ? a.chain_group : 1, grp = ktile / G;
-  const bool ch_first = ktile - grp * G == 0, ch_last = ktile - grp * G == G - 1 || ktile == nkb_live - 1;
-  const bool ch_direct = CHAIN && nkb_live <= G;                // a single chain: its last block writes the caller's dq (scaled) itself
-  float* const part = a.dq_part + ((size_t)(CHAIN ? grp : ktile) * a.B * a.H + bh) * a.Lq * D;
-  int* const my_flag = CHAIN ? a.dq_flags + ((size_t)bh * nkb + ktile) * 4 + wave : nullptr;
-  const int* const up_flag = CHAIN && !ch_first ? a.dq_flags + ((size_t)bh * nkb + ktile - 1) * 4 + wave : nullptr;
-  float* const dq_out = CHAIN ? a.dq + (size_t)b * a.Lq * a.ldq + head * D : nullptr;
+  float* const part = a.dq_part + ((size_t)ktile * a.B * a.H + bh) * a.Lq * D;      // this key block's dQ partial
   if (nq > 0) {
     // ---- prologue: tiles 0 and 1 staged, tile 2 in registers --------------------------------------------------------------
 #pragma unroll
@@ -227,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
     if (DROP) hb = drop_rowkey(a.seed, (uint32_t)(bh * a.Lq + 4 * h)) + (uint32_t)(key >> 1) * 0x9E3779B9U + (kodd ? 16u * 0x85EBCA77U : 0u);    // (odd key: the pair's hashes of queries CR(8..15))
 
     f32x16 s, dp, dq;
-    f32x4 xo0[2], xo1[2], xprev[2];
+    f32x4 xo0[2], xo1[2];
     bf16x8 fr[2][2], ft[4][3];
     u32x4 pwv[2][2], gwv[3][2];
     f32x2 pe[8], pd[8], xx[8], ff[8];
@@ -273,39 +255,7 @@ __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
 #define XOS(i_)                                                                                                        \
   do {                                                                                                                 \
     const int q_ = (t - 2) * 32 + 8 * wave + 4 * (i_) + (lane >> 4);                                                   \
-    if (t >= 2 && q_ < a.Lq) {                                                                                         \
-      f32x4 v_ = xo0[i_] + xo1[i_];                                                                                    \
-      if (CHAIN) {                                                                                                     \
-        if (!ch_first) v_ = xprev[i_] + v_;                                                                            \
-        if (ch_last && ch_direct) *reinterpret_cast<f32x4*>(dq_out + (size_t)q_ * a.ldq + 4 * (lane & 15)) = v_ * 0.125f; \
-        else *reinterpret_cast<f32x4*>(part + (unsigned)(q_ * D + 4 * (lane & 15))) = v_;                              \
-      } else {                                                                                                         \
-        *reinterpret_cast<f32x4*>(part + (unsigned)(q_ * D + 4 * (lane & 15))) = v_;                                   \
-      }                                                                                                                \
-    }                                                                                                                  \
-  } while (0)
-// CHAIN: wait until the same wave of the previous key block has added tile t - 2, then fetch its running sum (sc1: served by L2,
-// never a stale L1 line); later, once this wave's own stores are acknowledged, publish the count
-#define XOP()                                                                                                          \
-  do {                                                                                                                 \
-    if (CHAIN && !ch_first && t >= 2) {                                                                                \
-      int spins_ = 0;                                                                                                  \
-      while (__hip_atomic_load(up_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < t - 1 && ++spins_ < (1 << 20))   \
-        __builtin_amdgcn_s_sleep(2);                                                                                   \
-      _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                               \
-        const int q_ = (t - 2) * 32 + 8 * wave + 4 * i_ + (lane >> 4);                                                 \
-        const float* src_ = part + (unsigned)(min(q_, a.Lq - 1) * D + 4 * (lane & 15));                                \
-        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(xprev[i_]) : "v"(src_) : "memory");                  \
-      }                                                                                                                \
-    }                                                                                                                  \
-  } while (0)
-#define XOW() do { if (CHAIN && !ch_first && t >= 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(xprev[0]), "+v"(xprev[1]) : : "memory"); } while (0)
-#define XSIG()                                                                                                         \
-  do {                                                                                                                 \
-    if (CHAIN && !ch_last && t >= 2) {                                                                                 \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
-      if (lane == 0) __hip_atomic_store(my_flag, t - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                   \
-    }                                                                                                                  \
+    if (t >= 2 && q_ < a.Lq) *reinterpret_cast<f32x4*>(part + (unsigned)(q_ * D + 4 * (lane & 15))) = xo0[i_] + xo1[i_]; \
   } while (0)
 #define CRC(r_) (((r_) & 3) + 8 * ((r_) >> 2))
 // Dropout decisions, one hash per KEY PAIR (common.h drop_hash: the low 16 bits decide the even key, the high ones the odd key): the two
@@ -453,9 +403,7 @@ __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
     {                                             // the last tile's dQ (written in iteration nq)
       const int t = nq + 1;
       XOL(0); XOL(1);
-      XOP(); XOW();
       XOS(0); XOS(1);
-      XSIG();
     }
   }
   uint32_t gmax = 0u;
@@ -484,7 +432,7 @@ __global__ __launch_bounds__(256, 1) void emu_attn_bwd4h_kernel(EmuAttn a) {
 int attention_bwd4h_emu_launch(const EmuAttn& a, hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) {
-    const void* ks[2] = {reinterpret_cast<const void*>(emu_attn_bwd4h_kernel<true, false>), reinterpret_cast<const void*>(emu_attn_bwd4h_kernel<false, false>)};
+    const void* ks[2] = {reinterpret_cast<const void*>(emu_attn_bwd4h_kernel<true>), reinterpret_cast<const void*>(emu_attn_bwd4h_kernel<false>)};
     for (const void* kf : ks)
       if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B4H_LDS_BYTES) != hipSuccess) {
         set_error("attention_bwd_emu (f16x2): cannot raise the dynamic LDS limit to %u bytes", B4H_LDS_BYTES);
@@ -493,8 +441,8 @@ int attention_bwd4h_emu_launch(const EmuAttn& a, hipStream_t st) {
     attr_set = true;
   }
   const dim3 grid(cdiv(a.Lk, 128) * 8 * cdiv(a.B * a.H, 8));
-  if (a.drop_p > 0.f) hipLaunchKernelGGL((emu_attn_bwd4h_kernel<true, false>), grid, dim3(256), B4H_LDS_BYTES, st, a);
-  else hipLaunchKernelGGL((emu_attn_bwd4h_kernel<false, false>), grid, dim3(256), B4H_LDS_BYTES, st, a);
+  if (a.drop_p > 0.f) hipLaunchKernelGGL((emu_attn_bwd4h_kernel<true>), grid, dim3(256), B4H_LDS_BYTES, st, a);
+  else hipLaunchKernelGGL((emu_attn_bwd4h_kernel<false>), grid, dim3(256), B4H_LDS_BYTES, st, a);
   return check_launch("attention_bwd_emu (bwd4h)");
 }
 

@@ -53,15 +53,9 @@ struct Ctx {
   bool ok() const { return rc == HOISDF_OK; }
 };
 
-// HOISDF_EMU_SMALL=0: small-M linear layers stay on the exact-f32 tiled kernel (the round-3 flow; A/B runs)
-inline bool emu_small_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("HOISDF_EMU_SMALL"); on = (e && atoi(e) == 0) ? 0 : 1; }
-  return on == 1;
-}
 // small row counts (decoder stack, heads): the one-wave-per-tile emulated form (gemm_emu_small.hip)
 inline bool emu_small(const Ctx& c, long M, const float* a, long lda, const float* W, long ldw, int N, int K) {
-  if (!c.emu || !emu_small_enabled() || M > hoisdf_linear_emu_small_max_rows() || N % 4 || K % 4 || lda % 4 || ldw % 4) return false;
+  if (!c.emu || M > hoisdf_linear_emu_small_max_rows() || N % 4 || K % 4 || lda % 4 || ldw % 4) return false;
   return c.dry || hoisdf_linear_emu_small_supported(a, lda, W, ldw, M, N, K);
 }
 bool emu_rows(const Ctx& c, long M, const float* a, long lda, int contraction) {
@@ -135,7 +129,7 @@ void lin_bwd_weight(Ctx& c, const float* dy, int lddy, const uint32_t* bits, flo
     }
     return;
   }
-  if (c.emu && emu_small_enabled() && M <= hoisdf_linear_emu_small_max_rows()) {       // (no alignment demands: scalar loads)
+  if (c.emu && M <= hoisdf_linear_emu_small_max_rows()) {       // (no alignment demands: scalar loads)
     if (!c.dry) c.rc = hoisdf_linear_bwd_weight_emu_small(dy, lddy, bits, p, x, ldx, dW, K_pad, db, M, N, K_pad, c.stream);
     return;
   }

@@ -417,75 +417,10 @@ __device__ __forceinline__ bool lattice_keep(const float (&p)[3], const float* c
   return (u > bb[0]) && (u < bb[2]) && (v > bb[1]) && (v < bb[3]);      // strict (main/model.py:293-300)
 }
 
-__global__ __launch_bounds__(256) void lattice_count_kernel(const float* __restrict__ center,
-                                                            const float* __restrict__ cam_intr,
-                                                            const float* __restrict__ bbox, float scale,
-                                                            int n, float v32, int32_t* __restrict__ counts) {
-  const int b = blockIdx.y;
-  const int total = n * n * n;
-  int idx = blockIdx.x * 256 + threadIdx.x;
-  bool keep = false;
-  if (idx < total) {
-    float p[3];
-    lattice_point(idx, n, v32, p);
-    keep = lattice_keep(p, center + b * 3, cam_intr + b * 9, bbox + b * 4, scale);
-  }
-  unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counts[b], __popcll(m));
-}
-
-// one 1024-thread workgroup per sample walks the lattice in order -> deterministic ascending
-// lattice order of the survivors (what boolean indexing yields in the reference).
-__global__ __launch_bounds__(1024) void lattice_fill_kernel(const float* __restrict__ center,
-                                                            const float* __restrict__ cam_intr,
-                                                            const float* __restrict__ bbox, float scale,
-                                                            int n, float v32,
-                                                            const int32_t* __restrict__ offsets,
-                                                            float* __restrict__ points,
-                                                            int32_t* __restrict__ sample_idx,
-                                                            int32_t* __restrict__ lattice_idx) {
-  __shared__ int wave_cnt[16];
-  __shared__ int running;
-  const int b = blockIdx.x;
-  const int total = n * n * n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) running = offsets[b];
-  __syncthreads();
-  for (int base = 0; base < total; base += 1024) {
-    const int idx = base + threadIdx.x;
-    float p[3] = {0.f, 0.f, 0.f};
-    bool keep = false;
-    if (idx < total) {
-      lattice_point(idx, n, v32, p);
-      keep = lattice_keep(p, center + b * 3, cam_intr + b * 9, bbox + b * 4, scale);
-    }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int pre = running;
-    for (int w = 0; w < wave; ++w) pre += wave_cnt[w];
-    if (keep) {
-      const int dst = pre + __popcll(m & ((1ULL << lane) - 1ULL));
-      points[(size_t)dst * 3 + 0] = p[0];
-      points[(size_t)dst * 3 + 1] = p[1];
-      points[(size_t)dst * 3 + 2] = p[2];
-      if (sample_idx) sample_idx[dst] = b;
-      if (lattice_idx) lattice_idx[dst] = idx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; ++w) s += wave_cnt[w];
-      running += s;
-    }
-    __syncthreads();
-  }
-}
-
-// Round 6: the same two passes with the lattice cut into CHUNKS of 4096 consecutive indices per sample (64 chunks at 64^3): one 256-thread
-// block per (chunk, sample) instead of one 1024-thread block per sample (16 of the 256 CUs at B = 16: 434 us per call) and instead of
-// one atomic per WAVE on the sample's counter (4096 adds per address: 134 us per call).  The order of the survivors is the ascending
-// lattice order as before (chunks ascending, ascending inside a chunk): outputs bit-identical to the kernels above.
+// Count and fill with the lattice cut into CHUNKS of 4096 consecutive indices per sample (64 chunks at 64^3): one 256-thread block per
+// (chunk, sample).  One block per sample used 16 of the 256 CUs at B = 16 (434 us per call), and one atomic per WAVE on the sample's
+// counter made 4096 adds per address (134 us per call).  The survivors come out in ascending lattice order (chunks ascending, ascending
+// inside a chunk): what boolean indexing yields in the reference.
 constexpr int LCH = 4096;
 // survivors of this block's chunk (all threads return it); keep[i] = candidate chunk_base + 256 i + tid
 __device__ __forceinline__ int lattice_chunk_eval(const float* c, const float* K, const float* bb, float scale, int n, float v32, int chunk,
@@ -642,9 +577,7 @@ int hoisdf::project_gather_fwd_mag(const hoisdf_pyramid* pyr, const float* point
   if (n_rows == 0) return HOISDF_OK;
   ProjArgs a{points, sample_idx, n_rows, rows_per_sample, center, cam_intr, scale,
              (float)(img_w - 1) * 0.5f, (float)(img_h - 1) * 0.5f};
-  static int old_form = -1;                       // HOISDF_GATHER_FWD=1: the round-1 loop for every width (A/B runs)
-  if (old_form < 0) { const char* e = getenv("HOISDF_GATHER_FWD"); old_form = (e && atoi(e) == 1) ? 1 : 0; }
-  if (P.C4 <= 256 && !old_form)
+  if (P.C4 <= 256)
     hipLaunchKernelGGL(gather_fwd4_kernel, dim3(grid_for_rows(n_rows)), dim3(256), 0, as_stream(stream), P, a, feat, ldf, cam_out, uv_out, feat_mag);
   else
     hipLaunchKernelGGL(gather_fwd_kernel, dim3(grid_for_rows(n_rows)), dim3(256), 0, as_stream(stream), P, a, feat, ldf, cam_out, uv_out, feat_mag);
@@ -719,13 +652,6 @@ extern "C" int hoisdf_project_gather_bwd(const hoisdf_pyramid_grad* dpyr, const 
   return check_launch("gather_bwd");
 }
 
-// HOISDF_LATTICE=1: the round-1 kernels (one block per sample; A/B runs)
-static bool lattice_old_form() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("HOISDF_LATTICE"); v = (e && atoi(e) == 1) ? 1 : 0; }
-  return v == 1;
-}
-
 extern "C" int hoisdf_lattice_count(const float* center, const float* cam_intr, const float* bbox, float scale,
                                     int bins_n, int B, int32_t* counts, void* stream) {
   HOISDF_REQUIRE(center && cam_intr && bbox && counts, HOISDF_ERR_INVALID, "lattice_count: null pointer");
@@ -738,11 +664,8 @@ extern "C" int hoisdf_lattice_count(const float* center, const float* cam_intr, 
   }
   const int total = bins_n * bins_n * bins_n;
   const float v32 = (float)(2.0 / (double)(bins_n - 1));
-  if (lattice_old_form())
-    hipLaunchKernelGGL(lattice_count_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, center, cam_intr, bbox, scale, bins_n, v32, counts);
-  else
-    hipLaunchKernelGGL(lattice_chunk_count_kernel, dim3(cdiv(total, LCH), B), dim3(256), 0, st, center, cam_intr, bbox, scale, bins_n, v32, counts,
-                       (int32_t*)nullptr);
+  hipLaunchKernelGGL(lattice_chunk_count_kernel, dim3(cdiv(total, LCH), B), dim3(256), 0, st, center, cam_intr, bbox, scale, bins_n, v32, counts,
+                     (int32_t*)nullptr);
   return check_launch("lattice_count");
 }
 
@@ -757,11 +680,10 @@ extern "C" int hoisdf_lattice_fill(const float* center, const float* cam_intr, c
   hipStream_t st = as_stream(stream);
   const int nchunk = cdiv((long)bins_n * bins_n * bins_n, LCH);
   // per-(sample, chunk) survivor counts: stream-ordered library scratch (the words live until the next call on this stream)
-  int32_t* cc = lattice_old_form() ? nullptr : reinterpret_cast<int32_t*>(mag_scratch(st, (long)B * nchunk));
+  int32_t* cc = reinterpret_cast<int32_t*>(mag_scratch(st, (long)B * nchunk));
   if (!cc) {
-    hipLaunchKernelGGL(lattice_fill_kernel, dim3(B), dim3(1024), 0, st, center, cam_intr, bbox, scale, bins_n, v32, offsets, points, sample_idx,
-                       lattice_idx);
-    return check_launch("lattice_fill");
+    set_error("lattice_fill: scratch allocation failed");
+    return HOISDF_ERR_LAUNCH;
   }
   hipLaunchKernelGGL(lattice_chunk_count_kernel, dim3(nchunk, B), dim3(256), 0, st, center, cam_intr, bbox, scale, bins_n, v32, (int32_t*)nullptr, cc);
   hipLaunchKernelGGL(lattice_chunk_fill_kernel, dim3(nchunk, B), dim3(256), 0, st, center, cam_intr, bbox, scale, bins_n, v32, offsets, cc, points,

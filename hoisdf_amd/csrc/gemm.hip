@@ -465,13 +465,9 @@ static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1
 
 // Workgroups per CU for a grid of `nwg` equal tiles on 256 CUs.  With the natural 4 per CU a grid of 1025..1536 tiles
 // runs one full round and leaves a half-empty second one; at 3 per CU the same grid is two full rounds (768 slots) and
-// 3 waves per SIMD still hide the hand-over (tools/mb_occ.py, forward: 1536 tiles +2...+9 %; 768 / 3072 / 4096 tiles
-// +-1 %; 2 per CU never wins; the split-k grad-weight grids lose at 3).  HOISDF_GEMM_OCC={2,3,4} overrides (experiments).
+// 3 waves per SIMD still hide the hand-over (forward: 1536 tiles +2...+9 %; 768 / 3072 / 4096 tiles +-1 %; 2 per CU
+// never wins; the split-k grad-weight grids lose at 3).
 static int pick_occupancy(int nwg, int splitk) {
-  if (const char* e = getenv("HOISDF_GEMM_OCC")) {
-    const int v = atoi(e);
-    if (v >= 2 && v <= 4) return v;
-  }
   return (splitk <= 1 && nwg > 1024 && nwg <= 1536) ? 3 : 4;
 }
 
@@ -484,7 +480,7 @@ static int launch_gemm(GemmArgs g, hipStream_t st) {
   g.vecA = aligned16(g.A) && (g.lda % 4 == 0) && (A_KC ? (g.k_per_split % 4 == 0) : true);
   g.vecB = aligned16(g.B) && (g.ldb % 4 == 0) && (B_KC ? (g.k_per_split % 4 == 0) : true);
   g.vecC = aligned16(g.C) && (g.ldc % 4 == 0) && (g.c_split_stride % 4 == 0);
-  // Measured A/B (tools/mb_ab.py, MI355X): the hoisted branch-free staging loop is +-0 on the forward, -5...-9 % on
+  // Measured A/B (MI355X): the hoisted branch-free staging loop is +-0 on the forward, -5...-9 % on
   // grad-input and -3...-6 % on large grad-weight problems (the guarded loop's wave-uniform fast path schedules better
   // there), but +4...+7 % on the grad-weight problems with <= 4 output tiles - so only those take it.
   g.nofast = !(!A_KC && !B_KC && g.tiles_m * g.tiles_n <= 4);
@@ -592,19 +588,9 @@ extern "C" int hoisdf_linear_fwd(const float* x, int ldx, const float* W, int ld
   g.act = act; g.drop_p = drop_p; g.inv_keep = 1.f / (1.f - drop_p); g.thresh = drop_threshold(drop_p); g.seed = seed;
   g.splitk = 1; g.k_per_split = ((K + BK - 1) / BK) * BK; g.atomic_out = 0;
   g.bits_out = relu_bits; g.ldbits = (N + 31) / 32;
-  // (round 6: off by default for the FORWARD - float atomics in an unfixed order made the regression heads' outputs differ in the last
-  // bit between two identical runs, and with them sample 0's MANO outputs between two batches that differ in the OTHER samples; what
-  // still takes this kernel in a forward are the ragged N = 3 / 6 / 10 heads on a few hundred rows: microseconds either way.
-  // HOISDF_FWD_SPLITK=1 brings it back for A/B runs)
-  static int fwd_splitk = -1;
-  if (fwd_splitk < 0) { const char* e = getenv("HOISDF_FWD_SPLITK"); fwd_splitk = (e && atoi(e) == 1) ? 1 : 0; }
-  if (fwd_splitk && act == 0 && relu_bits == nullptr) {
-    g.splitk = plan_small_splitk(cdiv(M, BM) * cdiv(N, BN), K, g.k_per_split);
-    if (g.splitk > 1) {
-      g.atomic_out = 1;
-      if (int rc = zero_rows(y, ldy, M, N, as_stream(stream))) return rc;
-    }
-  }
+  // The forward never splits k: float atomics in an unfixed order made the regression heads' outputs differ in the last bit between two
+  // identical runs, and with them sample 0's MANO outputs between two batches that differ in the OTHER samples.  What could use it in a
+  // forward are the ragged N = 3 / 6 / 10 heads on a few hundred rows: microseconds either way.
   return launch_gemm<true, true>(g, as_stream(stream));
 }
 

@@ -42,7 +42,6 @@ constexpr int TM = 256, TN = 128, KS = 16, NT = 256;
 constexpr int WN = TN / 2, NJ = WN / 32;
 constexpr int A_U4 = 3 * 2 * TM, B_U4 = 3 * 2 * TN, STAGE_U4 = A_U4 + B_U4;
 constexpr int NB = B_U4 / NT;
-constexpr unsigned LDS_BYTES = 2u * STAGE_U4 * 16u;        // 73 728
 
 // exact three-way split (native ext vectors only: arrays of HIP's uint4 / float4 structs end up in scratch)
 #define SPLIT1(x, i)                             \
@@ -369,109 +368,10 @@ __device__ __forceinline__ void emu_epilogue(const EmuArgs& g, f32x16 (&acc)[4][
   }
 }
 
-template <bool MASK>
-__global__ __launch_bounds__(NT, 2) void emu_kc_kernel(EmuArgs g) {
-  extern __shared__ __attribute__((aligned(16))) u32x4 lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, kh = lane >> 5;
-  const int t = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
-  const int tm = t / g.tiles_n, tn = t - tm * g.tiles_n;
-  const int m0 = tm * TM, n0 = tn * TN;
-  const int nslab = (g.K + KS - 1) / KS;
-  const int last = nslab - 1;
 
-  f32x16 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // staging: thread = row of the A tile (rows past M re-read the last row: their products only reach rows that are never
-  // stored); B image pieces tid + 256 q.  All loads are unconditional (a load behind a branch makes hipcc assume the shorter
-  // queue at the merge and wait for everything): the k tail is handled by clamping the address and zeroing the value.
-  const int arow_i = min(m0 + tid, g.M - 1);
-  const float* arow = g.A + (size_t)arow_i * g.lda;
-  const uint32_t* mrow = MASK ? g.abits + (size_t)arow_i * g.ldbits : nullptr;
-  const u32x4* bsrc = g.Bimg + (size_t)tn * nslab * B_U4 + tid;
-  const int kmax4 = g.K - 4;                       // K is a multiple of 4 (checked by the host)
-  float4 ra[4];
-  u32x4 rb[NB];
-  uint32_t rm = 0xffffffffu;
-#define LOAD_SLAB(sl)                                                                                                  \
-  do {                                                                                                                 \
-    _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                                      \
-        ra[q] = *reinterpret_cast<const float4*>(arow + min((sl) * KS + q * 4, kmax4));                                \
-    _Pragma("unroll") for (int q = 0; q < NB; ++q) rb[q] = bsrc[(size_t)(sl) * B_U4 + q * NT];                          \
-    if (MASK) rm = mrow[(sl) >> 1];                                                                                    \
-  } while (0)
-#define STORE_SLAB(st, sl)                                                                                             \
-  do {                                                                                                                 \
-    const int krem_ = g.K - (sl) * KS;                      /* valid k in this slab (>= 16 except in the last one) */  \
-    const uint32_t mb_ = MASK ? (rm >> (((sl) & 1) * 16)) : 0xffffu;                                                   \
-    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                                    \
-      float4 v_ = ra[q];                                                                                               \
-      if (MASK) {                                                                                                      \
-        v_.x = ((mb_ >> (4 * q + 0)) & 1u) ? v_.x * g.ascale : 0.f;                                                    \
-        v_.y = ((mb_ >> (4 * q + 1)) & 1u) ? v_.y * g.ascale : 0.f;                                                    \
-        v_.z = ((mb_ >> (4 * q + 2)) & 1u) ? v_.z * g.ascale : 0.f;                                                    \
-        v_.w = ((mb_ >> (4 * q + 3)) & 1u) ? v_.w * g.ascale : 0.f;                                                    \
-      }                                                                                                                \
-      if (4 * q >= krem_) v_ = make_float4(0.f, 0.f, 0.f, 0.f);                                                        \
-      ra[q] = v_;                                                                                                      \
-    }                                                                                                                  \
-    _Pragma("unroll") for (int c = 0; c < 2; ++c) {                                                                    \
-      bf16x8 p0, p1, p2;                                                                                               \
-      split3x8(ra[2 * c], ra[2 * c + 1], p0, p1, p2);                                                                  \
-      (st)[(0 * 2 + c) * TM + tid] = __builtin_bit_cast(u32x4, p0);                                                    \
-      (st)[(1 * 2 + c) * TM + tid] = __builtin_bit_cast(u32x4, p1);                                                    \
-      (st)[(2 * 2 + c) * TM + tid] = __builtin_bit_cast(u32x4, p2);                                                    \
-    }                                                                                                                  \
-    _Pragma("unroll") for (int q = 0; q < NB; ++q) (st)[A_U4 + tid + q * NT] = rb[q];                                   \
-  } while (0)
-
-  LOAD_SLAB(0);
-  STORE_SLAB(lds, 0);
-  LOAD_SLAB(min(1, last));
-  __syncthreads();
-
-  for (int s = 0; s < nslab; ++s) {
-    const u32x4* st = lds + (s & 1) * STAGE_U4;
-    u32x4* nx = lds + ((s + 1) & 1) * STAGE_U4;
-    const u32x4* sa = st + wm * 128 + l31;
-    const u32x4* sb = st + A_U4 + wn * WN + l31;
-    bf16x8 b0[NJ], b1[NJ], b2[NJ], a[4];
-#define RD_B(dst, p) _Pragma("unroll") for (int j = 0; j < NJ; ++j) dst[j] = __builtin_bit_cast(bf16x8, sb[((p) * 2 + kh) * TN + j * 32])
-#define RD_A(p) _Pragma("unroll") for (int i = 0; i < 4; ++i) a[i] = __builtin_bit_cast(bf16x8, sa[((p) * 2 + kh) * TM + i * 32])
-#define MM1(bx) _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j) acc[i][j] = MFB(a[i], bx[j], acc[i][j])
-    RD_B(b0, 0); RD_A(2);
-    // the next slab: registers -> the other stage (masked, converted); the slab after it -> registers (a whole slab of MFMAs
-    // to land).  Pinned here: hipcc otherwise sinks the loads to the end of the loop body.  Past the end the last slab is
-    // simply staged again into the stage nobody reads any more.
-    STORE_SLAB(nx, min(s + 1, last));
-    LOAD_SLAB(min(s + 2, last));
-    __builtin_amdgcn_sched_barrier(0);
-    MM1(b0);                                   // x2 y0            (small terms first)
-    RD_B(b1, 1); RD_A(1);
-    MM1(b1); MM1(b0);                          // x1 y1, x1 y0
-    RD_B(b2, 2); RD_A(0);
-    MM1(b2); MM1(b1); MM1(b0);                 // x0 y2, x0 y1, x0 y0
-    __syncthreads();
-  }
-#undef LOAD_SLAB
-#undef STORE_SLAB
-#undef RD_A
-#undef RD_B
-#undef MM1
-
-  emu_epilogue<TM, TN, NJ>(g, acc, lds, m0, n0, wm, wn, wave, lane, l31, kh, 1.f);
-}
-
-
-// ---- main loop, second form ("rotated", hand-interleaved, line-coalesced activation loads): same tile, product order and
-// epilogue as emu_kc_kernel (forward results are bit identical), but
+// ---- main loop ("rotated", hand-interleaved, line-coalesced activation loads): the tile and epilogue described at the top of
+// the file, products small terms first (x2 y0, x1 y1, x1 y0, x0 y2, x0 y1, x0 y0).  Against a plain double-buffered loop
+// (stage slab s + 1, barrier, 48 MFMAs; retired, profiles/r04_kc2_dw2_vs_round3_forms.txt) the forward results are bit identical, but
 //  * the six product groups of a slab are rotated by half a slab against the barrier: a phase = [x0 y2, x0 y1, x0 y0 of slab
 //    s - 1 | x2 y0, x1 y1, x1 y0 of slab s], so the 24 MFMAs right behind the barrier take fragments that were read BEFORE it and
 //    every fragment read of slab s is issued 4 ... 24 MFMAs ahead of its first use;
@@ -482,8 +382,9 @@ __global__ __launch_bounds__(NT, 2) void emu_kc_kernel(EmuArgs g) {
 //    staging writes that precede it in program order), which is why the two stages are two distinct __shared__ objects here;
 //  * the activation tile is loaded with FOUR LANES PER ROW (lane = row l / 4 of a 16-row group, 16-byte quad l % 4 of the
 //    slab's 64 bytes; four such items per thread): a wave instruction touches 16 cache lines instead of 64.  With thread =
-//    row (the first form) every global_load_dwordx4 asks the vector memory pipe for 64 different lines, 16 bytes of each: the
-//    ablations of round 4 (profiles/r04_kc2_ablation.txt) showed the loop running at 285 - 338 TF without staging and at
+//    slab's 64 bytes; four such items per thread): a wave instruction touches 16 cache lines instead of 64.  With thread =
+//    row (the retired first form) every global_load_dwordx4 asks the vector memory pipe for 64 different lines, 16 bytes of each: the
+//    ablations of round 4 (profiles/r04_kc2_ablation_loads.txt) showed the loop running at 285 - 338 TF without staging and at
 //    130 - 170 with the loads and LDS writes but WITHOUT any conversion arithmetic - the address / tag path, not the VALU,
 //    was the limiter.  A quad converts to 8 bytes per plane (ds_write_b64); rows of the second k-chunk are stored with
 //    bit 2 of the row flipped so that a 16-lane group's 4 rows x 2 chunks x 2 halves cover all 32 banks once.
@@ -1076,8 +977,9 @@ struct DwArgs {
 };
 }  // namespace
 
-// DTK = tile width along k: 256 (wave tile 128 x 128, 256 accumulators, one workgroup per CU) or 128 (wave tile 128 x 64, two
-// workgroups per CU: the conversion phase of one overlaps the MFMAs of the other; x patches on wave 2 only, wave 3 stages nothing)
+// DTK = tile width along k: 128 (wave tile 128 x 64, two workgroups per CU: the conversion phase of one overlaps the MFMAs of the
+// other; x patches on wave 2 only, wave 3 stages nothing) is the one instantiated, for K <= 128.  The body also holds the 256-wide
+// tile (wave tile 128 x 128, one workgroup per CU), which emu_dw2_kernel / emu_dw2h_kernel replaced.
 template <bool MASK, int DTK>
 __global__ __launch_bounds__(NT, DTK == 256 ? 1 : 2) void emu_dw_kernel(DwArgs g) {
   constexpr int NJ = DTK / 64;                         // 32-column blocks per wave along k
@@ -1268,7 +1170,7 @@ __global__ __launch_bounds__(NT, DTK == 256 ? 1 : 2) void emu_dw_kernel(DwArgs g
 }
 
 // ---- grad-weight, second form ("rotated", hand-interleaved; 256 x 256 tiles): same partial-tile plan, product order and
-// epilogue as emu_dw_kernel<MASK, 256> (results are bit identical without a sign bitmap), with the main loop rebuilt the way
+// epilogue as emu_dw_kernel (results are bit identical without a sign bitmap), with the main loop rebuilt the way
 // emu_kc2_kernel's was - here it matters more, because this kernel runs ONE wave per SIMD (256 accumulators) and nothing else
 // covers a wave's conversion phase:
 //  * a phase = [x1 y1, x1 y0, x2 y0 of slab s - 1 | x0 y2, x0 y1, x0 y0 of slab s] between two barriers (96 MFMAs): the 48 MFMAs
@@ -1839,29 +1741,15 @@ bool emu_form_h2() { return form_h2(); }
 
 namespace {
 int launch_emu(EmuArgs g, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(emu_kc_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(emu_kc_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_BYTES) != hipSuccess) {
-      set_error("linear_emu: cannot raise the dynamic LDS limit to %u bytes", LDS_BYTES);
-      return HOISDF_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
   g.vecC = al16(g.C) && (g.ldc % 4 == 0);
   if (g.beta) g.amax_out = nullptr;           // (the tile is added to what is there: its own magnitude says nothing)
   if (form_h2()) {
     // tile width: 256 x 128, two workgroups per CU (the prologue / epilogue of one under the main loop of the other; finer tiles for
     // the 16 384 / 49 152-row shapes) except for the masked grad-input over a long contraction, where the 256 x 256 tile's halved
-    // staging work per MFMA wins (tools/mb_kc2.py, profiles/r05_h2_tile_widths.txt: 65536 x 1024 x 256 forward + ReLU + dropout
+    // staging work per MFMA wins (profiles/r05_h2_tile_widths.txt: 65536 x 1024 x 256 forward + ReLU + dropout
     // 180 vs 149 TF, 49152 x 512 x 512 247 vs 212, 65536 x 256 x 256 176 vs 159; masked grad-input over 1024: 172 vs 181).
-    // HOISDF_H2_TILE=128 / 256 forces one (A/B runs).
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("HOISDF_H2_TILE"); const int v = e ? atoi(e) : 0; forced = (v == 128 || v == 256) ? v : 0; }
     const bool wide_ok = cdiv(g.M, HTM) * cdiv(g.N, HTN) >= 208 && g.N % HTN == 0;
-    const bool narrow = forced ? forced == 128 : !(g.abits && g.K >= 768 && wide_ok);
+    const bool narrow = !(g.abits && g.K >= 768 && wide_ok);
     const int tw = narrow ? 128 : HTN;
     g.tiles_m = cdiv(g.M, HTM);
     g.tiles_n = cdiv(g.N, tw);
@@ -1889,16 +1777,11 @@ int launch_emu(EmuArgs g, hipStream_t st) {
   g.tiles_m = cdiv(g.M, TM);
   g.tiles_n = cdiv(g.N, TN);
   const dim3 grid((unsigned)(g.tiles_m * g.tiles_n)), block(NT);
-  static int form = -1;                       // HOISDF_EMU_KC=1: the first main-loop form (A/B runs); default: the rotated form
-  if (form < 0) { const char* e = getenv("HOISDF_EMU_KC"); form = (e && atoi(e) == 1) ? 1 : 2; }
-  if (form == 2) {
-    const bool kt = g.K % KS != 0 || (cdiv(g.K, KS) & 1);      // a pad slab (odd slab count) stages zeros through the k-tail test
-    if (g.abits && kt) hipLaunchKernelGGL((emu_kc2_kernel<true, true>), grid, block, 0, st, g);
-    else if (g.abits) hipLaunchKernelGGL((emu_kc2_kernel<true, false>), grid, block, 0, st, g);
-    else if (kt) hipLaunchKernelGGL((emu_kc2_kernel<false, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((emu_kc2_kernel<false, false>), grid, block, 0, st, g);
-  } else if (g.abits) hipLaunchKernelGGL((emu_kc_kernel<true>), grid, block, LDS_BYTES, st, g);
-  else hipLaunchKernelGGL((emu_kc_kernel<false>), grid, block, LDS_BYTES, st, g);
+  const bool kt = g.K % KS != 0 || (cdiv(g.K, KS) & 1);      // a pad slab (odd slab count) stages zeros through the k-tail test
+  if (g.abits && kt) hipLaunchKernelGGL((emu_kc2_kernel<true, true>), grid, block, 0, st, g);
+  else if (g.abits) hipLaunchKernelGGL((emu_kc2_kernel<true, false>), grid, block, 0, st, g);
+  else if (kt) hipLaunchKernelGGL((emu_kc2_kernel<false, true>), grid, block, 0, st, g);
+  else hipLaunchKernelGGL((emu_kc2_kernel<false, false>), grid, block, 0, st, g);
   return check_launch("linear_emu");
 }
 }  // namespace
@@ -2069,24 +1952,11 @@ int hoisdf::linear_bwd_input_emu_mag(const float* dy, int lddy, const uint32_t* 
 
 namespace {
 // row slices for grad-weight: one workgroup per CU (256 slots), >= 8 slabs per slice
-// k-tile width: 256 (one workgroup per CU, the rotated emu_dw2_kernel) unless K <= 128 (half of a 256-wide tile would be padding).
-// With the round-3 main loop (HOISDF_EMU_DW=1) the 128-wide form (two workgroups per CU) was the faster one for one or two output
-// tiles; the rotated loop reversed that (round 4, tools/mb_kc2.py: 65536 x 256 x 256 109 -> 118 TF, masked 92 -> 109;
-// 294912 x 256 x 256 123 -> 141 / 127 -> 150; 49152 x 512 x 256 124 -> 139).  HOISDF_EMU_DW_TILE=128 / 256 forces one form.
-bool dw_old_form() {
-  static int form = -1;
-  if (form < 0) { const char* e = getenv("HOISDF_EMU_DW"); form = (e && atoi(e) == 1) ? 1 : 2; }
-  return form == 1;
-}
-int dw_tile(int N, int K) {
-  static int forced = -1;
-  if (forced < 0) { const char* e = getenv("HOISDF_EMU_DW_TILE"); const int v = e ? atoi(e) : 0; forced = (v == 128 || v == 256) ? v : 0; }
-  if (forced) return forced;
-  if (dw_old_form()) return cdiv(N, DT) * cdiv(K, 256) <= 2 ? 128 : 256;
-  return K <= 128 ? 128 : 256;
-}
+// k-tile width: 256 (one workgroup per CU: the rotated emu_dw2_kernel / emu_dw2h_kernel) unless K <= 128, where half of a 256-wide tile
+// would be padding: emu_dw_kernel at its 128-wide tile, two workgroups per CU.
+int dw_tile(int K) { return K <= 128 ? 128 : 256; }
 void plan_dw(long M, int N, int K, int& splitk, int& mper) {
-  const int dtk = dw_tile(N, K);
+  const int dtk = dw_tile(K);
   const int ntile = cdiv(N, DT) * cdiv(K, dtk);
   const int slabs = cdiv(M, KS);
   const int slots = dtk == 256 ? 256 : 512;
@@ -2145,7 +2015,7 @@ int bwd_weight_emu(const float* dy, int lddy, const uint32_t* relu_bits, float d
   if (!attr_set) {
     bool ok = true;
 #define DW_ATTR(M_, T_) ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(emu_dw_kernel<M_, T_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2u * (3 * 2 * DT + 3 * 2 * T_) * 16u)) == hipSuccess
-    DW_ATTR(false, 256); DW_ATTR(true, 256); DW_ATTR(false, 128); DW_ATTR(true, 128);
+    DW_ATTR(false, 128); DW_ATTR(true, 128);
 #undef DW_ATTR
     if (!ok) {
       set_error("linear_bwd_weight_emu: cannot raise the dynamic LDS limit");
@@ -2157,7 +2027,7 @@ int bwd_weight_emu(const float* dy, int lddy, const uint32_t* relu_bits, float d
   g.dy = dy; g.lddy = lddy; g.x = x; g.ldx = ldx;
   g.bits = relu_bits; g.ldbits = (N + 31) / 32; g.ascale = 1.f / (1.f - drop_p);
   g.M = (int)M; g.N = N; g.K = K;
-  const int dtk = dw_tile(N, K);
+  const int dtk = dw_tile(K);
   g.tiles_n = cdiv(N, DT); g.tiles_k = cdiv(K, dtk);
   plan_dw(M, N, K, g.splitk, g.m_per_split);
   const long need = g.splitk > 1 ? (long)g.splitk * ((long)N * K + N) : 0;
@@ -2172,8 +2042,7 @@ int bwd_weight_emu(const float* dy, int lddy, const uint32_t* relu_bits, float d
   const int ntile = g.tiles_n * g.tiles_k;
   const dim3 grid((unsigned)(ntile * 8 * cdiv(g.splitk, 8))), block(NT);
   const unsigned lb = 2u * (3 * 2 * DT + 3 * 2 * dtk) * 16u;
-  const int form = dw_old_form() ? 1 : 2;     // HOISDF_EMU_DW=1: the first main-loop form for the 256-wide tiles (A/B runs)
-  if (dtk == 256 && form == 2 && h2) {
+  if (dtk == 256 && h2) {
     g.dy_amax = dy_mag; g.x_amax = x_mag;
     if (!dy_mag) {
       uint32_t* part = mag_scratch(st, M);
@@ -2194,15 +2063,12 @@ int bwd_weight_emu(const float* dy, int lddy, const uint32_t* relu_bits, float d
     else if (relu_bits) hipLaunchKernelGGL((emu_dw2h_kernel<true, false>), grid, block, 0, st, g);
     else if (hasdb) hipLaunchKernelGGL((emu_dw2h_kernel<false, true>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((emu_dw2h_kernel<false, false>), grid, block, 0, st, g);
-  } else if (dtk == 256 && form == 2) {
+  } else if (dtk == 256) {
     const bool hasdb = g.colsum != nullptr;
     if (relu_bits && hasdb) hipLaunchKernelGGL((emu_dw2_kernel<true, true>), grid, block, 0, st, g);
     else if (relu_bits) hipLaunchKernelGGL((emu_dw2_kernel<true, false>), grid, block, 0, st, g);
     else if (hasdb) hipLaunchKernelGGL((emu_dw2_kernel<false, true>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((emu_dw2_kernel<false, false>), grid, block, 0, st, g);
-  } else if (dtk == 256) {
-    if (relu_bits) hipLaunchKernelGGL((emu_dw_kernel<true, 256>), grid, block, lb, st, g);
-    else hipLaunchKernelGGL((emu_dw_kernel<false, 256>), grid, block, lb, st, g);
   } else {
     if (relu_bits) hipLaunchKernelGGL((emu_dw_kernel<true, 128>), grid, block, lb, st, g);
     else hipLaunchKernelGGL((emu_dw_kernel<false, 128>), grid, block, lb, st, g);

@@ -48,13 +48,7 @@ bool attn_h2_enabled() {
   if (on < 0) { const char* e = getenv("HOISDF_ATTN_FORM"); on = (e && (e[0] == 'b' || e[0] == 'B')) ? 0 : 1; }
   return on == 1;
 }
-// HOISDF_QKV_PLANES=0: the in-projection writes f32 q / k / v and the attention entry converts them (the round-3 flow; A/B runs)
-bool qkv_planes_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("HOISDF_QKV_PLANES"); on = (e && atoi(e) == 0) ? 0 : 1; }
-  return on == 1;
-}
-// The layout of `saved` depends on g.fused_qkv, which reads process-wide switches (hoisdf_set_gemm_emu, HOISDF_QKV_PLANES): the
+// The layout of `saved` depends on g.fused_qkv, which reads process-wide switches (hoisdf_set_gemm_emu, HOISDF_ATTN_FORM): the
 // forward records its decision per saved buffer and the backward of that buffer takes it from here, so a switch flipped between a
 // layer's forward and its backward (bench.py and the cfg.gemm_emu setter do flip it at run time) cannot make the two carve differently.
 struct SavedForms {
@@ -89,7 +83,7 @@ int geometry(const hoisdf_encoder_layer_desc* d, Geo& g) {
   // heads of 64, whole 128-token wave tiles per sample, the in-projection on the emulated GEMM
   // (f16x2 attention: where the layer's contractions run in the f16x2 form - the same test as layer_mags() below)
   g.att_h2 = attn_h2_enabled() && g.att == 2 && g.E == g.H * 64 && gemm_emu_mode() && emu_form_h2() && g.M >= EMU_MIN_ROWS;
-  g.fused_qkv = !g.att_h2 && qkv_planes_enabled() && g.att == 2 && (g.att_bwd_emu || !d->training) && g.E == g.H * 64 && g.S % 128 == 0 &&
+  g.fused_qkv = !g.att_h2 && g.att == 2 && (g.att_bwd_emu || !d->training) && g.E == g.H * 64 && g.S % 128 == 0 &&
                 g.nq % 128 == 0 && gemm_emu_mode() && g.M >= EMU_MIN_ROWS;
   return HOISDF_OK;
 }

@@ -680,12 +680,6 @@ __global__ __launch_bounds__(256) void residual_dropout_kernel(const float* __re
 
 using namespace hoisdf;
 
-// HOISDF_LN_ROWS=1: add + LayerNorm with one row per wave in flight for every width (the round-1 kernels; A/B runs)
-static bool ln_one_row_form() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("HOISDF_LN_ROWS"); v = (e && atoi(e) == 1) ? 1 : 0; }
-  return v == 1;
-}
 static int row_grid(long n_rows) {
   long blocks = (n_rows + 3) / 4;
   if (blocks > 256L * 8) blocks = 256L * 8;
@@ -813,7 +807,7 @@ int hoisdf::add_layernorm_fwd_mag(const float* x, const float* r, const float* g
   HOISDF_REQUIRE(D > 0 && D <= 1024 && (D & 3) == 0 && drop_p >= 0.f && drop_p < 1.f, HOISDF_ERR_INVALID,
                  "add_layernorm_fwd: D=%d must be a multiple of 4 and <= 1024", D);
   if (M == 0) return HOISDF_OK;
-  if (D <= 256 && !ln_one_row_form()) {
+  if (D <= 256) {
     int blocks = cdiv(M, 4 * LN_NR);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(add_ln_fwd256_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), x, r, gamma, beta, y, mean, rstd, M, D, eps, drop_p,
@@ -845,7 +839,7 @@ extern "C" int hoisdf_layernorm_rows_fwd(const float* x, const float* gamma, con
                  HOISDF_ERR_INVALID, "layernorm_rows_fwd: D=%d rows_per_group=%d take=%d", D, rows_per_group, take);
   const long M = groups * take;
   if (M == 0) return HOISDF_OK;
-  if (D <= 256 && !ln_one_row_form()) {
+  if (D <= 256) {
     int blocks = cdiv(M, 4 * LN_NR);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(add_ln_fwd256_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), x, (const float*)nullptr, gamma, beta, y, mean, rstd, M, D,
@@ -871,11 +865,10 @@ int hoisdf::add_layernorm_bwd_mag(const float* dy, const float* x, const float* 
   HOISDF_REQUIRE(D > 0 && D <= 1024 && (D & 3) == 0 && drop_p >= 0.f && drop_p < 1.f, HOISDF_ERR_INVALID,
                  "add_layernorm_bwd: D=%d must be a multiple of 4 and <= 1024", D);
   if (M == 0) return HOISDF_OK;
+  constexpr int cap = 1024;                     // blocks of the backward: 4 per CU
   int blocks = row_grid(M);
-  static int cap = -1;                          // HOISDF_LN_BWD_BLOCKS: blocks of the backward (A/B runs; default 1024 = 4 per CU)
-  if (cap < 0) { const char* e = getenv("HOISDF_LN_BWD_BLOCKS"); cap = e && atoi(e) > 0 ? atoi(e) : 1024; }
   if (blocks > cap) blocks = cap;
-  if (D <= 256 && !ln_one_row_form()) {
+  if (D <= 256) {
     blocks = cdiv(M, 4 * LN_NR);
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(add_ln_bwd256_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), dy, x, r, gamma, mean, rstd, dx, dr, dgamma, dbeta, M, D,
@@ -899,7 +892,7 @@ extern "C" int hoisdf_layernorm_rows_bwd(const float* dy, const float* x, const 
   if (M == 0) return HOISDF_OK;
   int blocks = row_grid(M);
   if (blocks > 512) blocks = 512;
-  if (D <= 256 && !ln_one_row_form()) {
+  if (D <= 256) {
     blocks = cdiv(M, 4 * LN_NR);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(add_ln_bwd256_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), dy, x, (const float*)nullptr, gamma, mean, rstd, dx,

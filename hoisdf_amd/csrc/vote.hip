@@ -332,10 +332,8 @@ extern "C" int hoisdf_vote_loss_fwd(const float* off, const float* cls, const fl
   HOISDF_REQUIRE(off && cls && pts && joint_gt_mm && joints && stats && l3d_sum && bce_sum && near_sum,
                  HOISDF_ERR_INVALID, "vote_loss_fwd: null pointer");
   HOISDF_REQUIRE(L > 0 && B > 0 && P > 0 && J > 0 && J <= 64, HOISDF_ERR_INVALID, "vote_loss_fwd: bad sizes");
-  // few (depth, sample) pairs and many points: segments of the points in separate blocks + an ordered merge (HOISDF_VOTE_SPLIT=0: never)
-  static int split_on = -1;
-  if (split_on < 0) { const char* e = getenv("HOISDF_VOTE_SPLIT"); split_on = (e && atoi(e) == 0) ? 0 : 1; }
-  int nseg = split_on ? min(cdiv(P, 512), max(1, 512 / (L * B))) : 1;
+  // few (depth, sample) pairs and many points: segments of the points in separate blocks + an ordered merge
+  const int nseg = min(cdiv(P, 512), max(1, 512 / (L * B)));
   float* scratch = nullptr;
   if (nseg > 1) scratch = reinterpret_cast<float*>(mag_scratch(as_stream(stream), (long)L * B * nseg * (5 * J + 3)));
   if (nseg > 1 && scratch) {

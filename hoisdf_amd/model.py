@@ -283,9 +283,8 @@ class Model(nn.Module):
                 # round-robin: once a RCCL process group has created its streams, a normal-priority second stream lands on
                 # the compute stream's queue and the two never overlap (measured with world 1 through RCCL: 95.6 vs 91.3
                 # ms/step, zero concurrent kernels in the trace; GPU_MAX_HW_QUEUES=8 cures it as well).  Without a process
-                # group the priority changes nothing (92.8 vs 92.9 ms/step).  HOISDF_SIDE_PRIORITY=0: normal priority.
-                prio = 0 if os.environ.get("HOISDF_SIDE_PRIORITY") == "0" else -1
-                self._side_stream = torch.cuda.Stream(device=root.device, priority=prio)
+                # group the priority changes nothing (92.8 vs 92.9 ms/step).
+                self._side_stream = torch.cuda.Stream(device=root.device, priority=-1)
             side = self._side_stream
         on_side = (lambda: torch.cuda.stream(side)) if two else contextlib.nullcontext
         want_sdf_loss = training or c.dataset == "dexycb"                                # :370-402
@@ -578,8 +577,7 @@ class Model(nn.Module):
         side = None
         if two:
             if getattr(self, "_side_stream", None) is None:
-                prio = 0 if os.environ.get("HOISDF_SIDE_PRIORITY") == "0" else -1
-                self._side_stream = torch.cuda.Stream(device=root.device, priority=prio)
+                self._side_stream = torch.cuda.Stream(device=root.device, priority=-1)     # (high priority: see hot_path)
             side = self._side_stream
         return ops.pose_infer(prepared, pyr, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
                               meta_info["bbox_obj"], counts, side, debug)

@@ -15,13 +15,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-import os
-
 from .. import ops
-
-# one autograd node per encoder layer (ops.encoder_layer); HOISDF_FUSED_LAYERS=0 keeps the op-by-op graph (A/B, debugging)
-FUSED_LAYER_NODES = os.environ.get("HOISDF_FUSED_LAYERS", "1") != "0"
-INTER_ROWS = os.environ.get("HOISDF_INTER_ROWS", "1") != "0"        # A/B switch: inter_norm on the kept rows only
 
 
 class MLP(nn.Module):
@@ -199,20 +193,14 @@ class TransformerEncoder(nn.Module):
             if n_keep is not None and n_keep < x.shape[1]:
                 x, inter = x[:, :n_keep].contiguous(), [y[:, :n_keep] for y in inter]
             return x, torch.stack(inter)
-        if FUSED_LAYER_NODES:
-            # one autograd node per layer (+ its inter_norm): multi-consumer gradients are summed inside the kernels
-            for i, l in enumerate(self.layers):
-                a = l.self_attn
-                x, y = ops.encoder_layer(x, n_keep if i == last else None, l.p if l.training else 0.0, a.num_heads,
-                                         a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
-                                         l.norm1.weight, l.norm1.bias, l.linear1.weight, l.linear1.bias, l.linear2.weight,
-                                         l.linear2.bias, l.norm2.weight, l.norm2.bias, n.weight, n.bias, l.norm1.eps,
-                                         n_inter=n_keep if INTER_ROWS else None)   # inter_norm only on the rows the caller reads
-                inter.append(y if n_keep is None or y.shape[1] == n_keep else y[:, :n_keep])
-            return x, torch.stack(inter)
-        for i, layer in enumerate(self.layers):
-            x = layer(x, n_keep if i == last else None)
-            y = ops.add_layernorm(x, None, n.weight, n.bias, n.eps)
+        # one autograd node per layer (+ its inter_norm): multi-consumer gradients are summed inside the kernels
+        for i, l in enumerate(self.layers):
+            a = l.self_attn
+            x, y = ops.encoder_layer(x, n_keep if i == last else None, l.p if l.training else 0.0, a.num_heads,
+                                     a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+                                     l.norm1.weight, l.norm1.bias, l.linear1.weight, l.linear1.bias, l.linear2.weight,
+                                     l.linear2.bias, l.norm2.weight, l.norm2.bias, n.weight, n.bias, l.norm1.eps,
+                                     n_inter=n_keep)                             # inter_norm only on the rows the caller reads
             inter.append(y if n_keep is None or y.shape[1] == n_keep else y[:, :n_keep])
         return x, torch.stack(inter)            # memory (B,S|n_keep,D), intermediates (L,B,S|n_keep,D)
 
@@ -278,7 +266,7 @@ class TransformerDecoder(nn.Module):
         B = memory.shape[0]
         n = self.norm
         l0 = self.layers[0]
-        if FUSED_LAYER_NODES and not self.normalize_before and ops.decoder_layer_ok(l0.p if l0.training else 0.0, memory, query_embed, l0.linear1.weight):
+        if not self.normalize_before and ops.decoder_layer_ok(l0.p if l0.training else 0.0, memory, query_embed, l0.linear1.weight):
             # one C-ABI call per layer and direction (csrc/layers.hip hoisdf_decoder_layer_fwd / _bwd)
             x = torch.zeros(B, query_embed.shape[0], query_embed.shape[1], device=memory.device)
             outs = []

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -141,9 +142,6 @@ def _rows(x: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 # pyramid handling
 # ---------------------------------------------------------------------------------------------
-_SHARED_PYR_GRAD = __import__("os").environ.get("HOISDF_SHARED_PYR_GRAD", "1") != "0"      # A/B switch
-
-
 class PyramidNHWC:
     """The feature pyramid in the layout the kernels want: per level a contiguous
     [B][H][W][C] float32 tensor (a zero-copy view when the encoder ran channels_last)."""
@@ -166,7 +164,7 @@ class PyramidNHWC:
         summed (15 adds over 3 x 130 MB + 4 x 130 MB of fills at B = 32).  The returned pyramid routes all of them into ONE set
         of zeroed buffers (float atomics already accumulate) that a sink node hands to the encoder once, after the last
         gather backward.  No-op without gradients and in deterministic mode (the order-fixed gather owns its output)."""
-        if not (torch.is_grad_enabled() and any(l.requires_grad for l in self.levels)) or deterministic() or not _SHARED_PYR_GRAD:
+        if not (torch.is_grad_enabled() and any(l.requires_grad for l in self.levels)) or deterministic():
             return self
         acc = _PyrAcc([tuple(l.shape) for l in self.levels], self.levels[0].device)
         out = PyramidNHWC(list(_PyrSink.apply(acc, *self.levels)))
@@ -283,10 +281,10 @@ def project_gather(pyr: PyramidNHWC, points, center, cam_intr, scale, img_hw=(25
 # linear
 # ---------------------------------------------------------------------------------------------
 # ---- fp32 emulated on the bf16 MFMA pipe (csrc/gemm_emu.hip): forward / grad-input of the large linear layers ------------
-_GEMM_EMU = __import__("os").environ.get("HOISDF_GEMM", "emu") != "f32"
+_GEMM_EMU = os.environ.get("HOISDF_GEMM", "emu") != "f32"
 _GEMM_EMU_MIN_ROWS = 2048            # below this a problem is a handful of tiles: latency-bound, stays on the f32 kernel
 _GEMM_EMU_DW_MIN_ROWS = 8192         # grad-weight: the contraction runs over the rows (>= 32 slabs per slice at 256 slices)
-_GEMM_EMU_DW_MIN_WIDTH = int(__import__("os").environ.get("HOISDF_EMU_DW_MIN_WIDTH", "64"))
+_GEMM_EMU_DW_MIN_WIDTH = 64
 _EMU_IMAGES = {}                     # (device, data_ptr, shape, ld, transpose) -> [image, version key, event, build stream, owner, reader streams]
 _EMU_PURGE_AT = [4096]
 
@@ -305,7 +303,6 @@ def gemm_emu() -> bool:
     return _GEMM_EMU
 
 
-_EMU_SMALL = __import__("os").environ.get("HOISDF_EMU_SMALL", "1") != "0"
 _EMU_SMALL_MAX = [None]
 
 
@@ -318,7 +315,7 @@ def _emu_small_max_rows() -> int:
 
 def _emu_small_ok(M: int, a: torch.Tensor, lda: int, W: torch.Tensor, N: int, K: int) -> bool:
     """small row counts (the 17-query decoder stack, the heads): the one-wave-per-tile emulated kernels (hoisdf_linear_*_emu_small)"""
-    if not (_GEMM_EMU and _EMU_SMALL):
+    if not _GEMM_EMU:
         return False
     return (1 <= M <= _emu_small_max_rows() and N % 4 == 0 and K % 4 == 0 and lda % 4 == 0 and W.stride(0) % 4 == 0
             and a.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0)
@@ -345,15 +342,14 @@ def _emu_purge() -> None:
 
 _EMU_EPOCH = [0]                     # bumped whenever an entry joins or leaves _EMU_IMAGES: the batch table is rebuilt
 _EMU_TABLE = {}                      # device index -> (epoch, keys, device table, n, total_blocks)
-_EMU_BATCH = __import__("os").environ.get("HOISDF_EMU_BATCH_PREP", "1") != "0"
 
 
 def _emu_refresh_images() -> None:
     """After an optimizer step (bump_weight_generation): rebuild EVERY cached weight image whose parameter is alive in one launch
     per device (hoisdf_linear_emu_prepare_batch) on the current stream, instead of ~170 few-microsecond launches strewn over the
     next step's critical path.  An entry keeps its device pointer (data_ptr is in the key), so the device-side table is built
-    once per cache composition.  HOISDF_EMU_BATCH_PREP=0: images are rebuilt one by one at their first use (the round-3 flow)."""
-    if not _EMU_BATCH or not _EMU_IMAGES:
+    once per cache composition."""
+    if not _EMU_IMAGES:
         return
     from ._lib import EmuPrepItem, lib
     import ctypes as C
@@ -524,14 +520,11 @@ def _gemm_bwd_input(dy2, lddy, bits, p, W, dx, lddx, M, N, K, accumulate, dy_mag
     return None
 
 
-# grad-weight form when no magnitude words are at hand: "b3" (bf16x3, needs none) or "h2" (f16x2, the library measures both operands)
-_EMU_DW_FORM = __import__("os").environ.get("HOISDF_EMU_DW_FORM", "b3")
-
-
 def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_scale=None, dy_scale=None, form=None, dy_mag=None, x_mag=None):
     """dW / db are zero-filled by the caller (the f32 kernel accumulates into them); the emulated form overwrites.
     form "h2" / magnitude words given (x_scale / dy_scale: what _gemm_fwd / _gemm_bwd_input returned for the same operands):
-    hoisdf_linear_bwd_weight_emu_mag (f16x2 where the process runs that form)."""
+    hoisdf_linear_bwd_weight_emu_mag (f16x2 where the process runs that form; operands without words are measured by the library).
+    No form and no magnitude words at hand: bf16x3, which needs none."""
     x_mag = x_mag if x_mag is not None else x_scale
     dy_mag = dy_mag if dy_mag is not None else dy_scale
     if _h2() and form != "b3":
@@ -543,7 +536,7 @@ def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_scale=None,
         from ._lib import lib
         nws = lib().hoisdf_linear_bwd_weight_emu_workspace(M, N, K)
         ws = torch.empty(max(nws, 4), device=dW.device, dtype=torch.float32)
-        if (form or _EMU_DW_FORM) == "h2" or dy_mag is not None or x_mag is not None:
+        if form == "h2" or dy_mag is not None or x_mag is not None:
             call("hoisdf_linear_bwd_weight_emu_mag", _p(dy2), lddy, _p(bits), float(p), _p(x2), ldx, _p(dW), K, _p(db), M, N, K,
                  _p(ws), nws, _p(dy_mag), _p(x_mag), _st())
         else:
@@ -552,7 +545,7 @@ def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_scale=None,
         return
     if M == 0:
         return                      # an empty row set: dW / db stay zero (what the f32 entry does)
-    if _GEMM_EMU and _EMU_SMALL and M <= _emu_small_max_rows():
+    if _GEMM_EMU and M <= _emu_small_max_rows():
         call("hoisdf_linear_bwd_weight_emu_small", _p(dy2), lddy, _p(bits), float(p), _p(x2), ldx, _p(dW), dW.stride(0), _p(db), M, N, K,
              _st())
         return
@@ -891,8 +884,9 @@ class _SdfQueryTrain(torch.autograd.Function):
         return (None,) * 10 + tuple(lg) + tuple(pg)
 
 
-_SDF_QUERY_TRAIN_C = __import__("os").environ.get("HOISDF_SDF_QUERY_TRAIN", "c") != "ops"
-_TOKENS_C = __import__("os").environ.get("HOISDF_TOKENS", "c") != "ops"           # coarse K7 + K8 / K11 + K12 entries
+# the coarse C entries; tests set these to False to compare them against the per-op composition
+_SDF_QUERY_TRAIN_C = True
+_TOKENS_C = True                     # coarse K7 + K8 / K11 + K12 entries
 
 
 def sdf_query_train_ok() -> bool:
@@ -1092,14 +1086,15 @@ def _attn_bwd(q, k, v, o, lse, do, dq, dk, dv, H, kv_len, drop_p, seed):
          _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H, Lq, Lk, kv_len, drop_p, seed, _st())
 
 
-_ATTENTION_EMU = __import__("os").environ.get("HOISDF_ATTENTION", "emu") != "f32"
+_ATTENTION_EMU = os.environ.get("HOISDF_ATTENTION", "emu") != "f32"
 
 
 def set_attention_emu(on: bool) -> None:
     """cfg.attention_emu (default on; HOISDF_ATTENTION=f32 turns it off): the large attention calls (forward with dropout + LSE,
-    fused one-pass backward) as fp32 emulated on the bf16 MFMA pipe - exact three-way bf16 splits of Q, K, V, dO, P and dS, six
-    products per product, f32 accumulation / softmax (csrc/attention_emu.hip).  fp32-equivalent results, no atomics.  Off: the
-    exact-f32 MFMA kernels of csrc/attention.hip."""
+    fused one-pass backward) as fp32 emulated on the 16-bit MFMA pipes, f32 accumulation / softmax (csrc/attention_emu*.hip).  Two
+    forms: f16x2 (default where the linear layers run it, _attn_h2: two scaled f16 pieces per operand, three products per product,
+    five where dS is an operand) and bf16x3 (HOISDF_ATTN_FORM=b3 / HOISDF_EMU_FORM=b3: exact three-way bf16 splits of Q, K, V, dO, P
+    and dS, six products per product).  fp32-equivalent results, no atomics.  Off: the exact-f32 MFMA kernels of csrc/attention.hip."""
     global _ATTENTION_EMU
     _ATTENTION_EMU = bool(on)
 
@@ -1109,9 +1104,9 @@ def attention_emu() -> bool:
 
 
 def _use_split(Lq: int) -> int:
-    """attention kernel family for a call with Lq queries: 0 = exact-f32 MFMA, 2 = bf16x3 emulated fp32 (default; family 1, the
-    f16 hi + lo split-precision training kernels of round 2, was retired in round 4: the emulated fp32 kernels are faster and
-    exact).  The 17-query decoder attention keeps its own f32 kernels."""
+    """attention kernel family for a call with Lq queries: 0 = exact-f32 MFMA, 2 = emulated fp32 (default; f16x2 when the caller
+    passes head magnitudes, else bf16x3; family 1, the split-precision training kernels of round 2, was retired in round 4).
+    The 17-query decoder attention keeps its own f32 kernels."""
     if Lq < 32:
         return 0
     return 2 if _ATTENTION_EMU else 0
@@ -1120,8 +1115,7 @@ def _use_split(Lq: int) -> int:
 # forward workspaces whose Q / K / V planes the matching backward reuses (hoisdf_attention_fwd_emu(keep = 1) ->
 # hoisdf_attention_bwd_emu(fwd_workspace)): keyed by the operands' addresses - the autograd node keeps q, k, v alive until its
 # backward, so a key cannot be taken over by another live call; leftovers of graphs that never ran backward go at the next step /
-# at 64 entries.  HOISDF_PLANES_KEEP=0 (or the older name HOISDF_SPLIT_KEEP=0): every backward converts on its own.
-_SPLIT_KEEP = __import__("os").environ.get("HOISDF_PLANES_KEEP", __import__("os").environ.get("HOISDF_SPLIT_KEEP", "1")) != "0"
+# at 64 entries.
 
 
 def _planes_key(q, k, v, H, kv_len):
@@ -1131,7 +1125,7 @@ def _planes_key(q, k, v, H, kv_len):
 _EMU_PLANES = {}
 
 
-_ATTN_FORM_H2 = __import__("os").environ.get("HOISDF_ATTN_FORM", "h2")[:1].lower() != "b"
+_ATTN_FORM_H2 = os.environ.get("HOISDF_ATTN_FORM", "h2")[:1].lower() != "b"
 
 
 def _attn_h2(rows: int) -> bool:
@@ -1147,7 +1141,6 @@ def _attn_fwd_emu(q, k, v, H, kv_len, drop_p, seed, keep=False, heads=None):
     Lk = k.shape[1]
     for t, L in ((q, Lq), (k, Lk), (v, Lk)):
         assert t.stride(2) == 1 and t.stride(0) == L * t.stride(1), "attention operands must be row-uniform views"
-    keep = keep and _SPLIT_KEEP
     nbytes = lib().hoisdf_attention_emu_workspace(B, H, Lq, Lk, 2 if keep else 0)
     ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
     o = torch.empty(B, Lq, E, device=q.device, dtype=torch.float32)
@@ -1187,14 +1180,14 @@ def _attn_bwd_emu(q, k, v, o, lse, do, dq, dk, dv, H, kv_len, drop_p, seed, head
          _p(delta), _p(dq), _p(dk), _p(dv), B, H, Lq, Lk, kv_len, float(drop_p), seed, _p(kept), _p(ws), nbytes, _st())
 
 
-_ATTN_BWD_EMU = __import__("os").environ.get("HOISDF_ATTN_BWD", "emu") != "f32"
+_ATTN_BWD_EMU = os.environ.get("HOISDF_ATTN_BWD", "emu") != "f32"
 
 
 def _emu_bwd() -> bool:
     """Emulated attention calls run their backward emulated as well (default; HOISDF_ATTN_BWD=f32 keeps the exact-f32 fused
-    backward next to the emulated forward): the 8-wave form of csrc/attention_emu.hip (16 keys per wave, two waves per SIMD)
-    measures 2.2 ms against 3.07 ms for the f32 kernel at B = 32, S = 2048 (tools/mb_attn_emu.py; the first, one-wave-per-SIMD
-    form was 3.4 ms).  It is order-fixed (no atomics), so it is also what deterministic mode uses."""
+    backward next to the emulated forward): the one-pass kernels of csrc/attention_emu_bwd4.hip (bf16x3) / attention_emu_bwd4h.hip
+    (f16x2) - four waves of 32 keys, one wave per SIMD, dQ through per-key-block partials and an ordered reduce pass.  They are
+    order-fixed (no atomics), so they are also what deterministic mode uses."""
     return _ATTN_BWD_EMU or deterministic()
 
 
@@ -1268,8 +1261,8 @@ _ATTENTION_F16_EVAL = False
 
 
 def set_attention_f16_eval(on: bool) -> None:
-    """BASELINE configs[4] ("fp16 MFMA attention"): route gradient-free, dropout-free attention calls through the f16
-    MFMA kernel (f32 accumulation / softmax).  Off by default: the f32 kernel is the parity configuration."""
+    """BASELINE configs[4] ("fp16 MFMA attention"): route gradient-free, dropout-free attention calls through the 16-bit-operand
+    kernel (bf16 hi + lo pairs, f32 accumulation / softmax).  Off by default: the f32 kernel is the parity configuration."""
     global _ATTENTION_F16_EVAL
     _ATTENTION_F16_EVAL = bool(on)
 
@@ -1281,21 +1274,12 @@ def _attn_fwd_f16(q, k, v, H, kv_len):
         assert t.stride(2) == 1 and t.stride(0) == L * t.stride(1), "attention operands must be row-uniform views"
     from ._lib import lib
     o = torch.empty(B, Lq, E, device=q.device, dtype=torch.float32)
-    if _ATTN16_LEGACY:              # HOISDF_ATTN16=f16: round 2's f16 hi + lo kernel (A/B runs)
-        nbytes = lib().hoisdf_attention_f16_workspace(B, H, Lk)
-        ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
-        call("hoisdf_attention_fwd_f16", _p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(o), E, B, H, Lq, Lk,
-             kv_len, _p(ws), nbytes, _st())
-        return o
-    # round 5: bf16 hi + lo operands on the pipelined forward (hoisdf_attention_fwd_bf16x2)
+    # bf16 hi + lo operands on the pipelined forward (hoisdf_attention_fwd_bf16x2)
     nbytes = lib().hoisdf_attention_bf16x2_workspace(B, H, Lq, Lk)
     ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
     call("hoisdf_attention_fwd_bf16x2", _p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(o), E, B, H, Lq, Lk,
          kv_len, _p(ws), nbytes, _st())
     return o
-
-
-_ATTN16_LEGACY = __import__("os").environ.get("HOISDF_ATTN16", "bf16x2") == "f16"
 
 
 def _use_f16(drop_p, *tensors) -> bool:
@@ -1633,7 +1617,7 @@ class _EncoderLayerC(torch.autograd.Function):
         nq = S if (n_query is None or n_query >= S) else int(n_query)
         ni = nq if (n_inter is None or n_inter >= nq) else int(n_inter)
         d = EncoderLayerDesc(B=B, S=S, E=E, F=w1.shape[0], H=H, n_query=nq, n_inter=ni, eps=eps, drop_p=p,
-                             attention=2 if _use_split(nq) == 2 else 0, attention_bwd_emulated=int(_emu_bwd() and _SPLIT_KEEP),
+                             attention=2 if _use_split(nq) == 2 else 0, attention_bwd_emulated=int(_emu_bwd()),
                              training=int(any(ctx.needs_input_grad)))
         for i in range(4):                                     # attention, after out-projection, FFN hidden, after the FFN
             d.seed[i] = next_seed() if p > 0 else 0
@@ -1692,17 +1676,14 @@ class _EncoderLayerC(torch.autograd.Function):
 
 
 _ENC_W_NAMES = ("w_in", "b_in", "w_out", "b_out", "g1", "be1", "w1", "b1", "w2", "b2", "g2", "be2", "g3", "be3")
-_ENCODER_LAYER_C = __import__("os").environ.get("HOISDF_ENCODER_LAYER", "c") != "ops"
+_ENCODER_LAYER_C = True              # tests set it to False to compare the C entry against the per-op node
 
 
 def _coarse_layer_ok(p, x, *weights) -> bool:
     """the C entry covers the default arithmetic; the opt-in split / f16 modes and bench.py's per-call event timing (which
     brackets the individual C-ABI calls from Python) take the op-by-op node"""
     from . import _lib
-    # (without kept planes the C entry's backward would fall back to the f32 kernel with dQ atomics: in deterministic mode the
-    # op-by-op node, whose emulated backward converts on its own, keeps the step order-fixed)
-    return (_ENCODER_LAYER_C and _lib._timer is None
-            and not _use_f16(p, x, *weights) and not (deterministic() and not _SPLIT_KEEP))
+    return _ENCODER_LAYER_C and _lib._timer is None and not _use_f16(p, x, *weights)
 
 
 def encoder_layer(x, n_query, p, H, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3, eps=1e-5,
@@ -1777,13 +1758,13 @@ class _DecoderLayerC(torch.autograd.Function):
         return (d_tgt, d_mem, d_qpos, None, None, None, None, None, *parts)
 
 
-_DECODER_LAYER_C = __import__("os").environ.get("HOISDF_DECODER_LAYER", "c") != "ops"
+_DECODER_LAYER_C = True              # as _ENCODER_LAYER_C
 
 
 def decoder_layer_ok(p, *tensors) -> bool:
     """as _coarse_layer_ok: default arithmetic only, and not while bench.py brackets the individual calls"""
     from . import _lib
-    return (_DECODER_LAYER_C and _lib._timer is None and not _use_f16(p, *tensors))
+    return _DECODER_LAYER_C and _lib._timer is None and not _use_f16(p, *tensors)
 
 
 def decoder_layer(tgt, memory, query_pos, mask_u8, kv_len, p, H, eps, *params):

@@ -414,20 +414,10 @@ int hoisdf_attention_bwd(const float* q, int ldq, const float* k, int ldk, const
                          const float* o, int ldo, const float* dout, int lddo, const float* lse,
                          float* delta, float* dq, float* dk, float* dv, int B, int H, int Lq, int Lk,
                          int kv_len, float drop_p, uint64_t seed, void* stream);
-/* Inference-only variant with f16 MFMA operands (BASELINE.json configs[4], "fp16 MFMA attention"): Q, K, V and the
- * probabilities are each split into f16 hi + lo parts (3 MFMA products per contraction, ~21 significant bits), both
- * products accumulate in f32 (v_mfma_f32_32x32x16_f16), softmax state in f32.  Same layouts and kv_len semantics as
- * hoisdf_attention_fwd; no dropout, no lse (not differentiable).  workspace: hoisdf_attention_f16_workspace(B, H, Lk)
- * bytes of device memory (f16 hi/lo copies of K and V^T), 16-byte aligned.  Error vs float64 attention < 1e-4 of
- * max|o| (tests); 1.8x the f32 kernel at 8192 keys.  The f32 entry point stays the parity configuration. */
-long hoisdf_attention_f16_workspace(int B, int H, int Lk);
-int hoisdf_attention_fwd_f16(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                             float* o, int ldo, int B, int H, int Lq, int Lk, int kv_len, void* workspace,
-                             long workspace_bytes, void* stream);
-
-/* The 16-bit-operand evaluation attention on the pipelined forward (round 5; what cfg.attention_f16_eval selects by default):
+/* The 16-bit-operand evaluation attention on the pipelined forward (BASELINE.json configs[4], "fp16 MFMA attention"; what
+ * cfg.attention_f16_eval selects):
  * Q, K, V and the probabilities as bf16 hi + lo pairs (two planes per operand: 16 significant bits, the f32 exponent range - none of
- * the f16 scheme's power-of-two scaling, no overflow at trained sigma gates), three v_mfma_f32_32x32x16_bf16
+ * an f16 hi + lo scheme's power-of-two scaling, no overflow at trained sigma gates), three v_mfma_f32_32x32x16_bf16
  * products per product, f32 softmax state and accumulation.  Same layouts and kv_len semantics as hoisdf_attention_fwd; no dropout,
  * no lse.  reference: nn.MultiheadAttention forward inside the encoder layers (common/nets/transformer.py:269), BASELINE.json
  * configs[4].  workspace: hoisdf_attention_bf16x2_workspace(B, H, Lq, Lk) bytes, 16-byte aligned. */

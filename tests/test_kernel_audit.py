@@ -26,14 +26,14 @@ def test_attention_backward_asm_mfma_hazard_audit(tmp_path):
     path = str(tmp_path / asm[0])
     text = open(path).read()
     kernels = re.findall(r"\.name:\s+(_ZN6hoisdf20emu_attn_bwd4_kernel\S+)", text)
-    assert len(set(kernels)) == 4, kernels                       # <DROP, CHAIN> x 2 x 2
+    assert len(set(kernels)) == 2, kernels                       # <DROP> x 2: every instantiation the library launches
     for m in re.finditer(r"\.name:\s+_ZN6hoisdf20emu_attn_bwd4_kernel.*?\.vgpr_spill_count:\s+(\d+)", text, re.S):
         assert int(m.group(1)) == 0
     for m in re.finditer(r"\.name:\s+_ZN6hoisdf20emu_attn_bwd4_kernel.*?\.private_segment_fixed_size:\s+(\d+)", text, re.S):
         assert int(m.group(1)) == 0
     a = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "audit_asm_mfma.py"), path, "bwd4_kernel"], capture_output=True, text=True)
     assert a.returncode == 0, a.stdout[-3000:]
-    assert a.stdout.count("MFMAs 120 findings 0") == 4, a.stdout
+    assert a.stdout.count("MFMAs 120 findings 0") == 2, a.stdout
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""emulated attention forward only: time at the step's shape, per library variant (HOISDF_LIB) / form (HOISDF_EMU_ATTN_FWD)"""
+"""emulated attention forward only: time at the step's shape, per library variant (HOISDF_LIB; LABEL names the line)"""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch

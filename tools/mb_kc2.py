@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of the two main-loop forms of the emulated forward / grad-input kernel (HOISDF_EMU_KC=1: first form, 2: rotated,
-hand-interleaved): per-shape time, and bit-equality of the outputs (same product order per accumulator)."""
+"""A/B of builds / forms of the emulated linear kernels (label=ENV1=v,ENV2=v ...; e.g. a variant library through HOISDF_LIB, or
+HOISDF_EMU_FORM=b3): per-shape time, bit-equality of the outputs against the first configuration, error vs fp64."""
 import sys, os, math, subprocess, json, hashlib
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 SHAPES = [(65536, 1024, 256), (65536, 256, 1024), (65536, 768, 256), (65536, 256, 256), (294912, 256, 256), (49152, 1024, 992),
@@ -71,8 +71,8 @@ def child():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "child":
         child(); sys.exit(0)
-    # configurations: label=ENV1=v,ENV2=v ... (default: the two forms of the built library)
-    cfgs = sys.argv[1:] or ["form1=HOISDF_EMU_KC=1", "form2=HOISDF_EMU_KC=2"]
+    # configurations: label=ENV1=v,ENV2=v ... (default: the two emulation forms of the built library)
+    cfgs = sys.argv[1:] or ["h2=", "b3=HOISDF_EMU_FORM=b3"]
     res = {}
     for rep in range(2):
         for c in cfgs:

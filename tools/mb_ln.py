@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""add + LayerNorm forward + backward at the encoder's shape (65536 x 256, dropout 0.1) for a few block caps of the backward
-(HOISDF_LN_BWD_BLOCKS; children):  python tools/mb_ln.py"""
-import os, subprocess, sys
+"""add + LayerNorm forward + backward at the encoder's shape (65536 x 256, dropout 0.1):  python tools/mb_ln.py
+(variants of the kernels: tools/build_variant.sh + HOISDF_LIB)"""
+import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def child():
+def main():
     import time, torch
     from hoisdf_amd import ops as O
     M, D = 65536, 256
@@ -28,9 +28,4 @@ def child():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "child":
-        child(); sys.exit(0)
-    for cap in (64, 128, 256, 512, 1024):
-        env = dict(os.environ, HOISDF_LN_BWD_BLOCKS=str(cap))
-        p = subprocess.run([sys.executable, __file__, "child"], env=env, capture_output=True, text=True)
-        print(cap, [l for l in p.stdout.splitlines() if l.startswith("RESULT")] or p.stderr[-500:])
+    main()

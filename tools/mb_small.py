@@ -26,7 +26,7 @@ for M, N, K in [(544, 256, 256), (544, 1024, 256), (544, 256, 1024), (544, 512, 
     bits = torch.empty(M, (N + 31) // 32, dtype=torch.int32, device=dev)
     row = []
     for small in (True, False):
-        O._EMU_SMALL = small
+        O.set_gemm_emu(small)          # off: every linear layer on the exact-f32 tiled kernel
         t1 = timeit(lambda: O._gemm_fwd(x, K, W, b, y, N, M, N, K, 1, 0.1, 1234, bits))
         t2 = timeit(lambda: O._gemm_bwd_input(dy, N, bits, 0.1, W, dx, K, M, N, K, 0))
         t3 = timeit(lambda: O._gemm_bwd_weight(dy, N, bits, 0.1, x, K, dW, db, M, N, K))

@@ -1,6 +1,6 @@
 #!/bin/bash
-# PMC comparison of the two main-loop forms of the emulated forward kernel (rocprofv3 --pmc only, one counter group per run).
-# usage (repo root, GPU box): tools/pmc_kc2.sh <outdir> [variant libs...]
+# PMC comparison of builds of the emulated forward kernel (rocprofv3 --pmc only, one counter group per run).
+# usage (repo root, GPU box): tools/pmc_kc2.sh <outdir> [label:ENV=v ...]   (e.g. v1:HOISDF_LIB=ab/lib_v1.so; the built library is always measured)
 R=$PWD; O=$R/$1; shift; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
@@ -14,7 +14,7 @@ PMCG=("SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
         "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TA_TCP_STATE_READ_sum TCP_GATE_EN2_sum"
         "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_REQ_sum"
         "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INSTS_SALU")
-for cfg in "form1:HOISDF_EMU_KC=1" "$@"; do
+for cfg in "built:" "$@"; do
   label=${cfg%%:*}; envs=${cfg#*:}
   for case in ${PMC_CASES:-linear_fwd_emu_65536x1024x256 linear_fwd_emu_65536x256x1024}; do
     i=0
