@@ -123,7 +123,9 @@ def reserve_hbm_pool(model: torch.nn.Module, fraction: float = 0.5, device=None)
     free, _ = torch.cuda.mem_get_info(dev)
     extra = min(int(fraction * peak), int(0.25 * free))
     streams = [torch.cuda.current_stream(dev)]
-    side = getattr(model, "_side_stream", None) or getattr(getattr(model, "module", None), "_side_stream", None)
+    side = getattr(model, "_side_stream", None)
+    if side is None:                    # (a wrapper around the Model)
+        side = getattr(getattr(model, "module", None), "_side_stream", None)
     if side is not None:
         streams.append(side)
     per = extra // len(streams) // (1 << 20) * (1 << 20)

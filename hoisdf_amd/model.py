@@ -14,6 +14,7 @@ Reference line numbers are cited per method.
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
 import random
 import weakref
@@ -63,6 +64,57 @@ _SDFQ_CACHE = weakref.WeakKeyDictionary()
 _POSE_CACHE = weakref.WeakKeyDictionary()
 
 
+@dataclasses.dataclass
+class _Field:
+    """One of the two point sets of a step.  Declared: what differs between the hand and the object copy of the per-field sequence
+    (the decoder follows from ``kind``; the input / bbox keys are ``{kind}_pre_points``, ``{kind}_sdf_points``, ``bbox_{kind}``).
+    Model._query_points, _field_step and _own_token_rows fill in the others: points (B,n,3) in the field's frame; sdf_pred (B,P,1)
+    on the SDF-loss points; feat (B n,C) gathered pixels, with gradient; cam (B,n,3) camera points; sdf (B,n,1) / pe (B,n,30) of the
+    points in their own field and x_sdf / x_pe re-centred in the other field, detached; fea (B,n,223) token-MLP output; tok (B,S,D)."""
+    kind: str                           # "hand" | "obj"
+    center: torch.Tensor                # (B,3) mano_root | obj_center_cam
+    scale: float                        # cfg.hand_sdf_scale | cfg.obj_sdf_scale
+    n: int                              # cfg.num_samp_hand | cfg.num_samp_obj
+    beta: nn.Parameter                  # hand_sigmoid_beta | obj_sigmoid_beta
+    points = sdf_pred = feat = cam = sdf = pe = x_sdf = x_pe = fea = tok = None
+
+
+class _StreamPlan:
+    """One- or two-stream issue of a step: THE decision (cfg.overlap_streams, HOISDF_TWO_STREAMS, single-stream in deterministic
+    mode; ``allow``: the caller's own condition) and the model's second stream, made on first use.  ``fork``: the side stream waits
+    for what the ambient one holds so far; ``join``: the ambient stream waits for the side stream; both take the tensors the
+    waiting stream will read of the other (None entries skipped).  With one stream they do nothing and ``on_side`` runs its block
+    in place.  Autograd replays every op's backward on its forward stream."""
+
+    def __init__(self, model, device, allow=True):
+        self.two = allow and bool(getattr(model.cfg, "overlap_streams", True)) and os.environ.get("HOISDF_TWO_STREAMS", "1") != "0" \
+            and not ops.deterministic()
+        if self.two and model._side_stream is None:
+            # HIGH priority = a hardware queue of its own.  HIP maps normal-priority streams onto 4 hardware queues
+            # round-robin: once a RCCL process group has created its streams, a normal-priority second stream lands on
+            # the compute stream's queue and the two never overlap (measured with world 1 through RCCL: 95.6 vs 91.3
+            # ms/step, zero concurrent kernels in the trace; GPU_MAX_HW_QUEUES=8 cures it as well).  Without a process
+            # group the priority changes nothing (92.8 vs 92.9 ms/step).
+            model._side_stream = torch.cuda.Stream(device=device, priority=-1)
+        self.side, self.cur = (model._side_stream, torch.cuda.current_stream(device)) if self.two else (None, None)
+
+    def on_side(self):
+        return torch.cuda.stream(self.side) if self.two else contextlib.nullcontext()
+
+    def fork(self, *made_on_cur):
+        self._edge(self.side, self.cur, made_on_cur)
+
+    def join(self, *made_on_side):
+        self._edge(self.cur, self.side, made_on_side)
+
+    def _edge(self, waiter, other, tensors):
+        if self.two:
+            waiter.wait_stream(other)
+            for t in tensors:
+                if t is not None:
+                    t.record_stream(waiter)
+
+
 class Model(nn.Module):
     def __init__(self, backbone_net, decoder_net, hand_sdf_decoder, obj_sdf_decoder, hand_transformer,
                  obj_transformer, mano_layer, cfg=_global_cfg):
@@ -104,6 +156,7 @@ class Model(nn.Module):
         self.freeze_stages()
         self._py_random = random            # the p < 0.4 branch draw (reference :426); injectable for tests
         self._jitter = None                 # test hook: callable(like, d) -> jitter tensor
+        self._side_stream = None            # the second HIP stream, made by the first two-stream _stream_plan
 
     def freeze_stages(self):
         if self.backbone_net is None:
@@ -253,6 +306,107 @@ class Model(nn.Module):
                 "obj": ops.sdf_infer_count_begin(meta_info["obj_center_cam"], K, meta_info["bbox_obj"], c.obj_sdf_scale, c.bins_n)}
 
     # ---- the hot path ----------------------------------------------------------------------
+    def _query_points(self, f: _Field, pyr, inputs, meta_info, branch_a, batch_ratio, counts):
+        """f.points: pre-sampled points + jitter (branch A), or the dense lattice's selection together with f.sdf / f.pe"""
+        if branch_a:
+            d = self.cfg.random_move_dist[len([a for a in self.cfg.random_ratio if batch_ratio > a])]
+            jit = self._jitter or (lambda like, dd: torch.empty_like(like).uniform_(-dd, dd))
+            f.points = inputs[f"{f.kind}_pre_points"] + jit(inputs[f"{f.kind}_pre_points"], d)
+        else:                                                                          # :462-481
+            f.points, f.sdf, f.pe, _ = self.sdf_infer(pyr, f.center, meta_info["cam_intr"], meta_info[f"bbox_{f.kind}"], f.scale, f.n,
+                                                      f.kind, (counts or {}).get(f.kind))
+
+    def _field_step(self, pyr, f: _Field, other: _Field, inputs, K, want_sdf_loss):
+        """The per-field sequence, on the stream the caller chose: SDF-loss prediction, gather, token MLP (op-by-op form), the
+        points in their own field (unless sdf_infer made that already) and re-centred in the ``other`` field."""
+        B = f.center.shape[0]
+        if want_sdf_loss:
+            f.sdf_pred, _, _ = self.sdf_forward(pyr, inputs[f"{f.kind}_sdf_points"], f.center, K, f.scale, f.kind)
+        # ONE gather of the points' pixels feeds the token MLP (with gradient), the own field and - the camera points being the same -
+        # the other field (the reference gathers them three times, :445/:486/:499; its detached queries run as single hoisdf_sdf_query_fwd calls)
+        f.feat, cam = ops.project_gather(pyr, f.points, f.center, K, f.scale, self.cfg.input_img_shape)
+        f.cam = cam.view(B, f.n, 3)
+        if not ops.tokens_ok(f.feat):           # (fused: K7 + K8 as one C call per point set, _own_token_rows)
+            f.fea = self.linear_transformerin(f.feat).view(B, f.n, -1)                                  # :486-493
+        fd = f.feat.detach()
+        if f.sdf is None:                       # the reference tracks these calls but only ever uses them detached
+            sdf, _, pe, _ = self._sdf_query(pyr, f.points, f.center, K, f.scale, f.kind, feat=fd)
+            f.sdf, f.pe = sdf.view(B, f.n, 1), pe.view(B, f.n, -1)
+        x_pts = (f.cam - other.center[:, None, :]) * other.scale                                        # :495-518
+        x_sdf, _, x_pe, _ = self._sdf_query(pyr, x_pts, other.center, K, other.scale, other.kind, feat=fd)
+        f.x_sdf, f.x_pe = x_sdf.view(B, f.n, 1), x_pe.view(B, f.n, -1)
+
+    def _own_token_rows(self, f: _Field):
+        """rows [0, n) of f.tok = [cam - center | pe | MLP(feat) * sigma(sdf, beta)].  Fused (hoisdf_tokens_fwd): makes the buffer
+        and f.fea (detached: for the other field's cross rows) as well; op-by-op: K8 into the existing buffer"""
+        if ops.tokens_ok(f.feat):
+            lin, c = self.linear_transformerin.layers, self.cfg
+            tok = torch.empty(f.center.shape[0], c.num_samp_hand + c.num_samp_obj, c.hidden_dim, device=f.center.device)
+            f.tok, fea = ops.tokens(tok, f.feat, f.cam, f.center, f.pe, f.sdf.detach(), f.beta, 0, [l.weight for l in lin], [l.bias for l in lin])
+            f.fea = fea.view(f.center.shape[0], f.n, -1)
+        else:
+            f.tok = ops.token_build(f.tok, f.cam.reshape(-1, 3), f.center, f.pe, f.fea, f.sdf.detach(), f.beta, 0)
+
+    def _assemble_tokens(self, hand: _Field, obj: _Field):
+        """token streams (batch-first).  The appended cross-field tokens are detached (:540,:558) and use
+        the *other* centre for xyz ("# bug" lines :498,:508 replicated)."""
+        fused = ops.tokens_ok(hand.feat)
+        if fused:
+            self._own_token_rows(hand)                  # (the object's: made on its own stream, right after its _field_step)
+        else:
+            hand.tok, obj.tok = (torch.empty(hand.center.shape[0], hand.n + obj.n, self.cfg.hidden_dim, device=hand.center.device)
+                                 for _ in range(2))
+        with torch.no_grad():                           # the cross rows [n, nh+no): the OTHER field's points in this field
+            for f, o in ((hand, obj), (obj, hand)):
+                ops.token_build(f.tok, o.cam.reshape(-1, 3), f.center, o.x_pe, o.fea.detach(), o.x_sdf, f.beta.detach(), f.n)
+        if not fused:
+            self._own_token_rows(hand)
+            self._own_token_rows(obj)
+
+    def _object_stack(self, obj: _Field):
+        """the object encoder stack and its two heads -> (obj_rot, obj_trans), each (L,B,no,3)"""
+        _, obj_enc = self.obj_transformer.forward_batch_first(obj.tok, n_keep=obj.n)       # :582-584
+        return self.linear_obj_rot(obj_enc), self.linear_obj_rel_trans(obj_enc)
+
+    def _mano_and_object_pose(self, hs, obj_rot, obj_trans, targets, training, loss, out):
+        """MANO head (two launches: ground truth, predictions + fused losses) + the object pose outputs and losses"""
+        c = self.cfg
+        if c.use_inverse_kinematics:                                               # :595-597
+            mano_shape = self.linear_shape(hs[:, :, 0])
+            out["mano_shape_out"] = mano_shape[-1]
+        else:                                                                      # :599-620
+            pose6d = self.linear_pose(hs[:, :, :c.mano_shape_indx])                # (L,B,16,6)
+            mano_shape = self.linear_shape(hs[:, :, c.mano_shape_indx])            # (L,B,10)
+            mp = targets["mano_param"] if (training or c.dataset == "dexycb") else None
+            pred_m, gt_m = self.mano_head.forward_batch_first(pose6d, mano_shape, mp)
+            out["mano_mesh_out"] = pred_m["verts3d"][-1]
+            out["mano_joints_out"] = pred_m["joints3d"][-1]
+            if c.dataset == "dexycb":
+                out["mano_joints_gt_out"] = gt_m["joints3d"]
+                out["mano_mesh_gt_out"] = gt_m["verts3d"]
+        if not training:                                                           # :622-624
+            out["obj_rot_out"] = obj_rot[-1].contiguous()
+            out["obj_trans_out"] = obj_trans[-1].contiguous()
+        if training or c.dataset == "dexycb":                                      # :640-654
+            if c.use_inverse_kinematics:
+                loss["shape_param_loss"], loss["shape_reg_loss"] = self.mano_shape_loss(mano_shape, targets["mano_param"][:, -10:])
+            else:
+                (loss["mano_mesh_loss"], loss["mano_joint_loss"], loss["pose_param_loss"],
+                 loss["shape_param_loss"], _, _) = self.mano_loss(pred_m, gt_m)
+        loss["obj_rot"] = ops.smooth_l1_loss_broadcast(obj_rot, targets["obj_rot"], c.num_samp_obj)            # :656-662 (a15: HIP reductions)
+        loss["obj_trans"] = ops.smooth_l1_loss_broadcast(obj_trans, targets["rel_obj_trans"], c.num_samp_obj)
+
+    def _hand_votes(self, hand_rel, hand_enc, targets, training, loss, out):
+        """hand vote heads + vote aggregation / losses"""
+        joints_gt = targets["joint_cam_no_trans"][:, 1:] if training or self.cfg.dataset == "dexycb" else \
+            torch.zeros(hand_rel.shape[0], 20, 3, device=hand_rel.device)              # :626-638
+        if ops.tokens_ok(hand_enc):             # K11 + K12 as one C call per direction (hoisdf_heads_vote_fwd / _bwd)
+            res = self.joints_vote_loss.forward_fused(hand_rel, hand_enc, self.linear_handvote, self.linear_handcls, joints_gt)
+        else:                                   # :587-593: the vote / cls MLPs (L,B,nh,60 / 20), then K12
+            res = self.joints_vote_loss(hand_rel, self.linear_handvote(hand_enc), self.linear_handcls(hand_enc), joints_gt, batch_first=True)
+        loss["loss_joint_3d"], loss["loss_joint_cls"], loss["loss_all_joint_3d"], joints = res
+        out["hand_joints_out"] = joints[-1]
+
     def hot_path(self, pyr: ops.PyramidNHWC, inputs, targets, meta_info, mode, epoch_cnt=1e8, batch_ratio=0, branch_a=None,
                  infer_counts=None):
         """reference :370-402 and :424-662: everything after decoder_net except the aux image losses.  ``branch_a`` /
@@ -262,33 +416,15 @@ class Model(nn.Module):
         training = mode == "train"
         if training:
             pyr = pyr.shared_grad()          # the step's four gather backwards scatter into ONE set of level gradients
-        loss: Dict[str, torch.Tensor] = {}
-        out: Dict[str, torch.Tensor] = {}
-        root, ocen, K = meta_info["mano_root"], meta_info["obj_center_cam"], meta_info["cam_intr"]
-        hs_, os_ = c.hand_sdf_scale, c.obj_sdf_scale
-        nh, no = c.num_samp_hand, c.num_samp_obj
-        B = root.shape[0]
-
+        loss, out = {}, {}
+        root, K = meta_info["mano_root"], meta_info["cam_intr"]
+        hand = _Field("hand", root, c.hand_sdf_scale, c.num_samp_hand, self.hand_sigmoid_beta)
+        obj = _Field("obj", meta_info["obj_center_cam"], c.obj_sdf_scale, c.num_samp_obj, self.obj_sigmoid_beta)
         # Everything that starts from the OBJECT points (their SDF query, input MLP, evaluation in the hand field and,
         # below, the object encoder stack) is independent of the hand-point work until the tokens are assembled: it is
-        # issued on a second HIP stream, so its small grids (16 384 rows) share the chip with the hand stream's kernels
-        # and kernel tails overlap.  Autograd replays every op's backward on its forward stream.
-        two = bool(getattr(c, "overlap_streams", True)) and root.is_cuda and os.environ.get("HOISDF_TWO_STREAMS", "1") != "0" \
-            and not ops.deterministic()
-        cur = side = None
-        if two:
-            cur = torch.cuda.current_stream(root.device)
-            if getattr(self, "_side_stream", None) is None:
-                # HIGH priority = a hardware queue of its own.  HIP maps normal-priority streams onto 4 hardware queues
-                # round-robin: once a RCCL process group has created its streams, a normal-priority second stream lands on
-                # the compute stream's queue and the two never overlap (measured with world 1 through RCCL: 95.6 vs 91.3
-                # ms/step, zero concurrent kernels in the trace; GPU_MAX_HW_QUEUES=8 cures it as well).  Without a process
-                # group the priority changes nothing (92.8 vs 92.9 ms/step).
-                self._side_stream = torch.cuda.Stream(device=root.device, priority=-1)
-            side = self._side_stream
-        on_side = (lambda: torch.cuda.stream(side)) if two else contextlib.nullcontext
+        # issued on a second HIP stream, so its small grids (16 384 rows) share the chip with the hand stream's kernels.
+        plan = _StreamPlan(self, root.device, allow=root.is_cuda)
         want_sdf_loss = training or c.dataset == "dexycb"                                # :370-402
-
         if branch_a is None:
             branch_a = self.draw_branch(mode, epoch_cnt)                               # :426-427
         if not branch_a and infer_counts is None:
@@ -296,175 +432,45 @@ class Model(nn.Module):
         log = getattr(self, "branch_log", None)
         if log is not None and training:
             log.append("A" if branch_a else "B")             # bench.py --branch-mix reports the mix it measured
-        if branch_a:
-            d = c.random_move_dist[len([a for a in c.random_ratio if batch_ratio > a])]
-            jit = self._jitter or (lambda like, dd: torch.empty_like(like).uniform_(-dd, dd))
-            hand_points = inputs["hand_pre_points"] + jit(inputs["hand_pre_points"], d)
-            obj_points = inputs["obj_pre_points"] + jit(inputs["obj_pre_points"], d)
-        else:                                                                          # :462-481
-            ic = infer_counts or {}
-            hand_points, hand_sdf, hand_pe, _ = self.sdf_infer(pyr, root, K, meta_info["bbox_hand"], hs_, nh, "hand", ic.get("hand"))
-            obj_points, obj_sdf, obj_pe, _ = self.sdf_infer(pyr, ocen, K, meta_info["bbox_obj"], os_, no, "obj", ic.get("obj"))
-        self.hand_sigmoid_beta.data.clamp_(min=2e-3)                                   # :124
-        self.obj_sigmoid_beta.data.clamp_(min=2e-3)
-
-        so = None
+        for f in (hand, obj):
+            self._query_points(f, pyr, inputs, meta_info, branch_a, batch_ratio, infer_counts)
+        for f in (hand, obj):
+            f.beta.data.clamp_(min=2e-3)                                               # :124
         # both streams read the cached SDF-query weight descriptors: (re)build them HERE, on the ambient stream and
-        # ahead of side.wait_stream, so neither stream can launch a query before the folded weights are written
-        self._query_weights("hand").get()
-        self._query_weights("obj").get()
-        if two:
-            side.wait_stream(cur)                       # the points, the pyramid, the inputs and the query weights are ready
-        with on_side():                                 # ---- object points ----
-            if want_sdf_loss:
-                so, _, _ = self.sdf_forward(pyr, inputs["obj_sdf_points"], ocen, K, os_, "obj")
-            # ONE gather of the object points' pixels feeds the token MLP (with gradient), the object field and - the
-            # camera points being the same - the evaluation of those points in the hand field (the reference gathers
-            # them three times, :445/:486/:499; its detached queries run as single hoisdf_sdf_query_fwd calls)
-            obj_feat, obj_cam = ops.project_gather(pyr, obj_points, ocen, K, os_, c.input_img_shape)
-            obj_cam = obj_cam.view(B, no, 3)
-            fused_tok = ops.tokens_ok(obj_feat)     # K7 + K8 as one C call per point set (hoisdf_tokens_fwd), issued once sdf / pe exist
-            if not fused_tok:
-                obj_fea = self.linear_transformerin(obj_feat).view(B, no, -1)                           # :486-493
-            fd = obj_feat.detach()
-            if branch_a:                # the reference tracks these calls but only ever uses them detached
-                obj_sdf, _, obj_pe, _ = self._sdf_query(pyr, obj_points, ocen, K, os_, "obj", feat=fd)
-                obj_sdf, obj_pe = obj_sdf.view(B, no, 1), obj_pe.view(B, no, -1)
-            obj_h_pts = (obj_cam - root[:, None, :]) * hs_                                              # :495-518
-            obj_h_sdf, _, obj_h_pe, _ = self._sdf_query(pyr, obj_h_pts, root, K, hs_, "hand", feat=fd)
-            obj_h_sdf, obj_h_pe = obj_h_sdf.view(B, no, 1), obj_h_pe.view(B, no, -1)
-            S, D = nh + no, c.hidden_dim
-            tin_w = [l.weight for l in self.linear_transformerin.layers]
-            tin_b = [l.bias for l in self.linear_transformerin.layers]
-            if fused_tok:                       # the object points' own token rows (+ their MLP output for the hand stream's cross rows)
-                obj_tok = torch.empty(B, S, D, device=root.device)
-                obj_tok, obj_fea = ops.tokens(obj_tok, obj_feat, obj_cam, ocen, obj_pe, obj_sdf.detach(), self.obj_sigmoid_beta, 0,
-                                              tin_w, tin_b)
-                obj_fea = obj_fea.view(B, no, -1)
-        # ---- hand points (ambient stream) ----
-        if want_sdf_loss:
-            sh, _, _ = self.sdf_forward(pyr, inputs["hand_sdf_points"], root, K, hs_, "hand")
-        hand_feat, hand_cam = ops.project_gather(pyr, hand_points, root, K, hs_, c.input_img_shape)
-        hand_cam = hand_cam.view(B, nh, 3)
-        if not fused_tok:
-            hand_fea = self.linear_transformerin(hand_feat).view(B, nh, -1)
-        fd = hand_feat.detach()
-        if branch_a:
-            hand_sdf, _, hand_pe, _ = self._sdf_query(pyr, hand_points, root, K, hs_, "hand", feat=fd)
-            hand_sdf, hand_pe = hand_sdf.view(B, nh, 1), hand_pe.view(B, nh, -1)
-        hand_rel = hand_cam - root[:, None, :]
-        hand_o_pts = (hand_cam - ocen[:, None, :]) * os_
-        hand_o_sdf, _, hand_o_pe, _ = self._sdf_query(pyr, hand_o_pts, ocen, K, os_, "obj", feat=fd)
-        hand_o_sdf, hand_o_pe = hand_o_sdf.view(B, nh, 1), hand_o_pe.view(B, nh, -1)
-        if two:
-            cur.wait_stream(side)
-            for t in (so, obj_sdf, obj_pe, obj_fea, obj_cam, obj_h_sdf, obj_h_pe):          # (obj_tok, when built there: below)
-                if t is not None:
-                    t.record_stream(cur)
+        # ahead of the fork, so neither stream can launch a query before the folded weights are written
+        for f in (hand, obj):
+            self._query_weights(f.kind).get()
+        plan.fork()                                     # the points, the pyramid, the inputs and the query weights are ready
+        with plan.on_side():                            # ---- object points ----
+            self._field_step(pyr, obj, hand, inputs, K, want_sdf_loss)
+            if ops.tokens_ok(obj.feat):         # fused: the object's own token rows here, the hand's after the join (_assemble_tokens)
+                self._own_token_rows(obj)
+        self._field_step(pyr, hand, obj, inputs, K, want_sdf_loss)                     # ---- hand points (ambient stream) ----
+        hand_rel = hand.cam - root[:, None, :]
+        plan.join(obj.sdf_pred, obj.sdf, obj.pe, obj.fea, obj.cam, obj.x_sdf, obj.x_pe, obj.tok)
         if want_sdf_loss:
             loss["sdfhand_loss"], loss["sdfobj_loss"] = self.sdf_loss(
-                sh, so, targets["hand_sdf"], targets["obj_sdf"], clamp=c.ClampingDistance)       # :393-402, clamp fused
-
-        # token streams (batch-first).  The appended cross-field tokens are detached (:540,:558) and use
-        # the *other* centre for xyz ("# bug" lines :498,:508 replicated).
-        S, D = nh + no, c.hidden_dim
-        dev = root.device
-        if fused_tok:
-            hand_tok = torch.empty(B, S, D, device=dev)
-            hand_tok, hand_fea = ops.tokens(hand_tok, hand_feat, hand_cam, root, hand_pe, hand_sdf.detach(), self.hand_sigmoid_beta, 0,
-                                            tin_w, tin_b)
-            hand_fea = hand_fea.view(B, nh, -1)
-            if two:
-                obj_tok.record_stream(cur)
-            with torch.no_grad():               # the cross rows, written into the buffers the two calls above returned
-                ops.token_build(hand_tok, obj_cam.reshape(-1, 3), root, obj_h_pe, obj_fea, obj_h_sdf,
-                                self.hand_sigmoid_beta.detach(), nh)
-                ops.token_build(obj_tok, hand_cam.reshape(-1, 3), ocen, hand_o_pe, hand_fea, hand_o_sdf,
-                                self.obj_sigmoid_beta.detach(), no)
-        else:
-            hand_tok = torch.empty(B, S, D, device=dev)
-            obj_tok = torch.empty(B, S, D, device=dev)
-            with torch.no_grad():
-                ops.token_build(hand_tok, obj_cam.reshape(-1, 3), root, obj_h_pe, obj_fea.detach(), obj_h_sdf,
-                                self.hand_sigmoid_beta.detach(), nh)
-                ops.token_build(obj_tok, hand_cam.reshape(-1, 3), ocen, hand_o_pe, hand_fea.detach(), hand_o_sdf,
-                                self.obj_sigmoid_beta.detach(), no)
-            hand_tok = ops.token_build(hand_tok, hand_cam.reshape(-1, 3), root, hand_pe, hand_fea, hand_sdf.detach(),
-                                       self.hand_sigmoid_beta, 0)
-            obj_tok = ops.token_build(obj_tok, obj_cam.reshape(-1, 3), ocen, obj_pe, obj_fea, obj_sdf.detach(),
-                                      self.obj_sigmoid_beta, 0)
-
+                hand.sdf_pred, obj.sdf_pred, targets["hand_sdf"], targets["obj_sdf"], clamp=c.ClampingDistance)   # :393-402, clamp fused
+        self._assemble_tokens(hand, obj)
         tgt_mask = None if c.use_inverse_kinematics else get_mano_tgt_mask(c)         # :564-569
         # Only rows < nh (hand stream) / < no (object stream) of the encoder outputs are ever read (:587-593 and
         # the memory mask), so the last layer of each stack skips the other query rows - same values, less work.
-        # The object encoder stack (+ its heads) goes to the second stream as well (127.3 -> 126.0 ms/step on its own).
-        if two:
-            side.wait_stream(cur)
-            obj_tok.record_stream(side)
-            with torch.cuda.stream(side):
-                _, obj_enc = self.obj_transformer.forward_batch_first(obj_tok, n_keep=no)      # :582-584
-                obj_rot = self.linear_obj_rot(obj_enc)                                         # (L,B,no,3)
-                obj_trans = self.linear_obj_rel_trans(obj_enc)
-        hs, memory, hand_enc = self.hand_transformer.forward_batch_first(
-            hand_tok, self.mano_query_embed.weight, tgt_mask, nh, n_keep=nh)           # :571-581
-        if two:
-            side.wait_stream(cur)                       # hs is ready; the side stream already holds the object stack
-            hs.record_stream(side)
-        else:
-            _, obj_enc = self.obj_transformer.forward_batch_first(obj_tok, n_keep=no)      # :582-584
-            obj_rot = self.linear_obj_rot(obj_enc)                                         # (L,B,no,3)
-            obj_trans = self.linear_obj_rel_trans(obj_enc)
-
-        # ---- MANO head (two launches: ground truth, predictions + fused losses) + the object pose losses, on the second
-        # stream under the big vote-head GEMMs of the ambient stream
-        pred_m = gt_m = None
-        side_made = []
-        with on_side():
-            if c.use_inverse_kinematics:                                               # :595-597
-                mano_shape = self.linear_shape(hs[:, :, 0])
-                out["mano_shape_out"] = mano_shape[-1]
-            else:                                                                      # :599-620
-                pose6d = self.linear_pose(hs[:, :, :c.mano_shape_indx])                # (L,B,16,6)
-                mano_shape = self.linear_shape(hs[:, :, c.mano_shape_indx])            # (L,B,10)
-                mp = targets["mano_param"] if (training or c.dataset == "dexycb") else None
-                pred_m, gt_m = self.mano_head.forward_batch_first(pose6d, mano_shape, mp)
-                out["mano_mesh_out"] = pred_m["verts3d"][-1]
-                out["mano_joints_out"] = pred_m["joints3d"][-1]
-                if c.dataset == "dexycb":
-                    out["mano_joints_gt_out"] = gt_m["joints3d"]
-                    out["mano_mesh_gt_out"] = gt_m["verts3d"]
-            if not training:                                                           # :622-624
-                out["obj_rot_out"] = obj_rot[-1].contiguous()
-                out["obj_trans_out"] = obj_trans[-1].contiguous()
-            if training or c.dataset == "dexycb":                                      # :640-654
-                if c.use_inverse_kinematics:
-                    loss["shape_param_loss"], loss["shape_reg_loss"] = self.mano_shape_loss(
-                        mano_shape, targets["mano_param"][:, -10:])
-                else:
-                    (loss["mano_mesh_loss"], loss["mano_joint_loss"], loss["pose_param_loss"],
-                     loss["shape_param_loss"], _, _) = self.mano_loss(pred_m, gt_m)
-            loss["obj_rot"] = ops.smooth_l1_loss_broadcast(obj_rot, targets["obj_rot"], no)            # :656-662 (a15: HIP reductions)
-            loss["obj_trans"] = ops.smooth_l1_loss_broadcast(obj_trans, targets["rel_obj_trans"], no)
+        # The object encoder stack (+ its heads) goes to the second stream as well (127.3 -> 126.0 ms/step on its own): with
+        # two streams it is issued AHEAD of the hand stack, with one stream behind it (dropout seeds follow the issue order).
+        plan.fork(obj.tok)
+        if plan.two:
+            with plan.on_side():
+                obj_rot, obj_trans = self._object_stack(obj)
+        hs, memory, hand_enc = self.hand_transformer.forward_batch_first(hand.tok, self.mano_query_embed.weight, tgt_mask, hand.n,
+                                                                         n_keep=hand.n)          # :571-581
+        plan.fork(hs)                                   # hs is ready; the side stream already holds the object stack
+        if not plan.two:
+            obj_rot, obj_trans = self._object_stack(obj)
+        with plan.on_side():                            # ---- under the big vote-head GEMMs of the ambient stream
+            self._mano_and_object_pose(hs, obj_rot, obj_trans, targets, training, loss, out)
             side_made = [t for t in list(loss.values()) + list(out.values()) if torch.is_tensor(t)]
-
-        # ---- hand vote heads + vote aggregation / losses (ambient stream)
-        if training or c.dataset == "dexycb":                                          # :626-638
-            joints_gt = targets["joint_cam_no_trans"][:, 1:]
-        else:
-            joints_gt = torch.zeros(B, 20, 3, device=dev)
-        if ops.tokens_ok(hand_enc):             # K11 + K12 as one C call per direction (hoisdf_heads_vote_fwd / _bwd)
-            (loss["loss_joint_3d"], loss["loss_joint_cls"], loss["loss_all_joint_3d"],
-             joints) = self.joints_vote_loss.forward_fused(hand_rel, hand_enc, self.linear_handvote, self.linear_handcls, joints_gt)
-        else:
-            hand_off = self.linear_handvote(hand_enc)                                  # :587-593 (L,B,nh,60)
-            hand_cls = self.linear_handcls(hand_enc)
-            (loss["loss_joint_3d"], loss["loss_joint_cls"], loss["loss_all_joint_3d"],
-             joints) = self.joints_vote_loss(hand_rel, hand_off, hand_cls, joints_gt, batch_first=True)
-        out["hand_joints_out"] = joints[-1]
-        if two:
-            cur.wait_stream(side)
-            for t in side_made:
-                t.record_stream(cur)
+        self._hand_votes(hand_rel, hand_enc, targets, training, loss, out)             # ---- (ambient stream)
+        plan.join(*side_made)
         return loss, out
 
     # ---- the same stage through ONE C-ABI call (include/hoisdf.h hoisdf_pose_infer; opt-in) ------------------------------
@@ -568,19 +574,12 @@ class Model(nn.Module):
         hand_joints_out, obj_rot_out, obj_trans_out and mano_mesh_out + mano_joints_out (or mano_shape_out for the IK variant),
         same keys and shapes as hot_path(..., "eval")'s outputs.  No losses, no ground-truth MANO outputs.  ``counts``: what
         infer_native_begin queued ahead of the encoder.  The default arithmetic only (cfg.attention_f16_eval is not offered)."""
-        c = self.cfg
         pyr = self._pyramid(pyr)
         root = meta_info["mano_root"]
         ops._chk(root, self.hand_sigmoid_beta)          # GPU tensors only: there is no CPU form of this path
         prepared = self._pose_prepared(root.shape[0], pyr.C, root.device)
-        two = bool(getattr(c, "overlap_streams", True)) and os.environ.get("HOISDF_TWO_STREAMS", "1") != "0" and not ops.deterministic()
-        side = None
-        if two:
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(device=root.device, priority=-1)     # (high priority: see hot_path)
-            side = self._side_stream
         return ops.pose_infer(prepared, pyr, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
-                              meta_info["bbox_obj"], counts, side, debug)
+                              meta_info["bbox_obj"], counts, _StreamPlan(self, root.device).side, debug)
 
     def infer_native_begin(self, meta_info, C_=None):
         """queue both survivor counts of infer_native (hoisdf_pose_infer_begin) - ahead of the image encoder, as infer_counts_begin"""
@@ -589,13 +588,25 @@ class Model(nn.Module):
         return ops.PoseInferCounts(prepared.desc, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
                                    meta_info["bbox_obj"])
 
-    def _forward_native(self, inputs, targets, meta_info):
-        """eval forward with the switch on: the encoder in PyTorch, then infer_native; dexycb keeps its ground-truth MANO outputs"""
+    def _set_arithmetic(self, f16_eval=None):
+        """the configuration's arithmetic switches -> ops (``f16_eval`` None: that one is left alone - infer_native does not offer it)"""
         c = self.cfg
+        if f16_eval is not None:
+            ops.set_attention_f16_eval(bool(getattr(c, "attention_f16_eval", False)) and f16_eval)
         if getattr(c, "gemm_emu", None) is not None:
             ops.set_gemm_emu(bool(c.gemm_emu))
         if getattr(c, "attention_emu", None) is not None:
             ops.set_attention_emu(bool(c.attention_emu))
+
+    @staticmethod
+    def _aux_outputs(out, targets, decoder_out):            # heat-map and segmentation maps next to their targets
+        out.update(joint_heatmap_out=decoder_out[:, 0], hand_seg_gt_out=targets["hand_seg"], hand_seg_pred_out=decoder_out[:, 1],
+                   obj_seg_gt_out=targets["obj_seg"], obj_seg_pred_out=decoder_out[:, 2])
+
+    def _forward_native(self, inputs, targets, meta_info):
+        """eval forward with the switch on: the encoder in PyTorch, then infer_native; dexycb keeps its ground-truth MANO outputs"""
+        c = self.cfg
+        self._set_arithmetic()
         with torch.no_grad():
             counts = self.infer_native_begin(meta_info, self.linear_sdfin.layers[0].weight.shape[1])
             img_feat, skips = self.backbone_net(inputs["img"])
@@ -605,11 +616,7 @@ class Model(nn.Module):
                 if not c.use_inverse_kinematics:
                     gv, gj, _ = ops.mano_gt(targets["mano_param"], self.mano_head.mano_layer.kernel_assets())
                     out["mano_joints_gt_out"], out["mano_mesh_gt_out"] = gj, gv
-                out["joint_heatmap_out"] = decoder_out[:, 0]
-                out["hand_seg_gt_out"] = targets["hand_seg"]
-                out["hand_seg_pred_out"] = decoder_out[:, 1]
-                out["obj_seg_gt_out"] = targets["obj_seg"]
-                out["obj_seg_pred_out"] = decoder_out[:, 2]
+                self._aux_outputs(out, targets, decoder_out)
         return out
 
     def forward(self, inputs, targets, meta_info, mode, epoch_cnt=1e8, batch_ratio=0):
@@ -622,18 +629,10 @@ class Model(nn.Module):
         img_feat, skips = self.backbone_net(inputs["img"])                            # :367-368 (PyTorch / MIOpen)
         feature_pyramid, decoder_out = self.decoder_net(img_feat, skips)
         pyr = self._pyramid(feature_pyramid)
-        ops.set_attention_f16_eval(bool(getattr(c, "attention_f16_eval", False)) and mode != "train")
-        if getattr(c, "gemm_emu", None) is not None:
-            ops.set_gemm_emu(bool(c.gemm_emu))
-        if getattr(c, "attention_emu", None) is not None:
-            ops.set_attention_emu(bool(c.attention_emu))
+        self._set_arithmetic(f16_eval=mode != "train")
         loss, out = self.hot_path(pyr, inputs, targets, meta_info, mode, epoch_cnt, batch_ratio, branch_a, infer_counts)
         if mode == "train" or c.dataset == "dexycb":                                   # :404-422 aux image losses
-            out["joint_heatmap_out"] = decoder_out[:, 0]
-            out["hand_seg_gt_out"] = targets["hand_seg"]
-            out["hand_seg_pred_out"] = decoder_out[:, 1]
-            out["obj_seg_gt_out"] = targets["obj_seg"]
-            out["obj_seg_pred_out"] = decoder_out[:, 2]
+            self._aux_outputs(out, targets, decoder_out)
             # (f4) one HIP pass: Gaussian heat-map target + MSE + the two BCE maps
             loss["joint_heatmap"], loss["obj_seg"], loss["hand_seg"], _ = ops.aux_image_losses(
                 decoder_out, targets["joint_coord"], targets["hand_seg"], targets["obj_seg"], c.sigma)
