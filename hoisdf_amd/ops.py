@@ -13,7 +13,10 @@ from typing import Optional, Sequence
 
 import torch
 
-from ._lib import Pyramid, call, lib
+from . import _lib
+from ._lib import (_DEC_W, _SDF_G, MLP_MAX_LAYERS, DecoderLayerDesc, DecoderLayerGrads, DecoderLayerWeights, EncoderLayerDesc,
+                   EncoderLayerGrads, EncoderLayerWeights, Mlp, MlpGrads, PoseOutputs, Pyramid, SdfWeightGrads, SdfWeights, call, lib)
+from .emu_images import WeightImageCache, prepare_batch_table
 
 _SEED = [0x9E3779B97F4A7C15, 0]
 _WEIGHT_GEN = [0]      # bumped by optimizers that update parameters behind autograd's back (FusedAdamW's HIP kernel does
@@ -23,18 +26,16 @@ _WEIGHT_GEN = [0]      # bumped by optimizers that update parameters behind auto
 def deterministic() -> bool:
     """HOISDF_DETERMINISTIC=1 / ops.set_deterministic(True): order-fixed forms of every accumulating kernel (see
     include/hoisdf.h hoisdf_set_deterministic); the model then also runs single-stream."""
-    from ._lib import lib
     return bool(lib().hoisdf_get_deterministic())
 
 
 def set_deterministic(on: bool) -> None:
-    from ._lib import lib
     lib().hoisdf_set_deterministic(int(bool(on)))
 
 
 def bump_weight_generation() -> None:
     _WEIGHT_GEN[0] += 1
-    _emu_refresh_images()
+    _EMU_CACHE.refresh(_WEIGHT_GEN[0])
 
 
 def manual_seed(seed: int) -> None:
@@ -102,11 +103,20 @@ def zero_arena_end_step() -> None:
     _ARENA.active = False
 
 
-zero_arena_disable = zero_arena_end_step
-
-
 def _zeros(n: int, device) -> torch.Tensor:
     return _ARENA.zeros(int(n), torch.device(device) if not isinstance(device, torch.device) else device)
+
+
+def _zero_views(shapes, device):
+    """ONE zero-filled buffer (a slice of the per-step arena when it is active) carved into one view per entry of ``shapes``
+    (an element count gives a flat view)"""
+    sizes = [n if isinstance(n, int) else math.prod(n) for n in shapes]
+    buf = _zeros(sum(sizes), device)
+    views, off = [], 0
+    for sh, n in zip(shapes, sizes):
+        views.append(buf[off:off + n].view(sh))
+        off += n
+    return views
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -172,13 +182,16 @@ class PyramidNHWC:
         return out
 
     def struct(self, tensors: Optional[Sequence[torch.Tensor]] = None) -> Pyramid:
-        ts = self.levels if tensors is None else tensors
-        s = Pyramid()
-        s.n_levels, s.B = len(ts), self.B
-        for i, t in enumerate(ts):
-            s.data[i] = t.data_ptr()
-            s.C[i], s.H[i], s.W[i] = t.shape[3], t.shape[1], t.shape[2]
-        return s
+        return _pyramid_struct(self.levels if tensors is None else tensors, self.B)
+
+
+def _pyramid_struct(levels: Sequence[torch.Tensor], B: int) -> Pyramid:
+    s = Pyramid()
+    s.n_levels, s.B = len(levels), B
+    for i, t in enumerate(levels):
+        s.data[i] = t.data_ptr()
+        s.C[i], s.H[i], s.W[i] = t.shape[3], t.shape[1], t.shape[2]
+    return s
 
 
 class _PyrAcc:
@@ -254,11 +267,7 @@ class _ProjectGather(torch.autograd.Function):
             acc.flat.record_stream(torch.cuda.current_stream(dfeat.device))
         else:
             grads = [torch.zeros(sh, device=dfeat.device, dtype=torch.float32) for sh in shapes]
-        g = Pyramid()
-        g.n_levels, g.B = len(grads), B
-        for i, t in enumerate(grads):
-            g.data[i] = t.data_ptr()
-            g.C[i], g.H[i], g.W[i] = t.shape[3], t.shape[1], t.shape[2]
+        g = _pyramid_struct(grads, B)
         call("hoisdf_project_gather_bwd", C.byref(g), _p(pts), _p(sample_idx), pts.shape[0], rps, _p(center),
              _p(cam_intr), scale, img_hw[0], img_hw[1], _p(dfeat), dfeat.shape[1], _st())
         if acc is not None:
@@ -285,8 +294,7 @@ _GEMM_EMU = os.environ.get("HOISDF_GEMM", "emu") != "f32"
 _GEMM_EMU_MIN_ROWS = 2048            # below this a problem is a handful of tiles: latency-bound, stays on the f32 kernel
 _GEMM_EMU_DW_MIN_ROWS = 8192         # grad-weight: the contraction runs over the rows (>= 32 slabs per slice at 256 slices)
 _GEMM_EMU_DW_MIN_WIDTH = 64
-_EMU_IMAGES = {}                     # (device, data_ptr, shape, ld, transpose) -> [image, version key, event, build stream, owner, reader streams]
-_EMU_PURGE_AT = [4096]
+_EMU_CACHE = WeightImageCache()      # the weight images of the emulated kernels (emu_images.py)
 
 
 def set_gemm_emu(on: bool) -> None:
@@ -295,7 +303,6 @@ def set_gemm_emu(on: bool) -> None:
     results (include/hoisdf.h hoisdf_linear_fwd_emu) at 1.7x the f32 MFMA kernel.  Off: the exact-f32 MFMA kernel."""
     global _GEMM_EMU
     _GEMM_EMU = bool(on)
-    from ._lib import lib
     lib().hoisdf_set_gemm_emu(int(_GEMM_EMU))            # the layers inside hoisdf_sdf_query_fwd follow
 
 
@@ -308,7 +315,6 @@ _EMU_SMALL_MAX = [None]
 
 def _emu_small_max_rows() -> int:
     if _EMU_SMALL_MAX[0] is None:
-        from ._lib import lib
         _EMU_SMALL_MAX[0] = lib().hoisdf_linear_emu_small_max_rows()
     return _EMU_SMALL_MAX[0]
 
@@ -326,121 +332,9 @@ def _emu_ok(M: int, a: torch.Tensor, lda: int, contraction: int) -> bool:
             and a.data_ptr() % 16 == 0)
 
 
-_EMU_GRAVEYARD = []                  # images of weights that no longer exist, kept for one more purge cycle (see _emu_purge)
-
-
-def _emu_purge() -> None:
-    """Drop the cache entries whose weight tensor is gone.  Never touches an entry whose owner is alive: callers (the coarse
-    encoder / decoder layer entries) hold only the raw device pointer of an image for the duration of their C call, so an
-    image must not be freed behind a live weight.  The purged images themselves are parked until the NEXT purge (thousands
-    of lookups later), far beyond any kernel that may still read them on another stream."""
-    _EMU_GRAVEYARD.clear()
-    for k in [k for k, e in _EMU_IMAGES.items() if e[4]() is None]:
-        _EMU_GRAVEYARD.append(_EMU_IMAGES.pop(k)[0])
-    _EMU_EPOCH[0] += 1
-
-
-_EMU_EPOCH = [0]                     # bumped whenever an entry joins or leaves _EMU_IMAGES: the batch table is rebuilt
-_EMU_TABLE = {}                      # device index -> (epoch, keys, device table, n, total_blocks)
-
-
-def _emu_refresh_images() -> None:
-    """After an optimizer step (bump_weight_generation): rebuild EVERY cached weight image whose parameter is alive in one launch
-    per device (hoisdf_linear_emu_prepare_batch) on the current stream, instead of ~170 few-microsecond launches strewn over the
-    next step's critical path.  An entry keeps its device pointer (data_ptr is in the key), so the device-side table is built
-    once per cache composition."""
-    if not _EMU_IMAGES:
-        return
-    from ._lib import EmuPrepItem, lib
-    import ctypes as C
-    by_dev = {}
-    for k, e in list(_EMU_IMAGES.items()):
-        base = e[4]()
-        if base is None:
-            continue
-        # the owner must still COVER the cached address: param.data = ..., module.to() / .float(), load_state_dict(assign=True) keep the
-        # Parameter object alive but free its old storage - the batch kernel must never read that
-        try:
-            st = base.untyped_storage()
-            lo = st.data_ptr()
-            ok = base.is_cuda and base.device.index == k[0] and lo <= k[1] and k[1] + 4 * ((k[2] - 1) * k[4] + k[3]) <= lo + st.nbytes()
-        except RuntimeError:
-            ok = False
-        if not ok:
-            _EMU_GRAVEYARD.append(_EMU_IMAGES.pop(k)[0])
-            _EMU_EPOCH[0] += 1
-            continue
-        by_dev.setdefault(k[0], []).append((k, e))
-    for dev, ents in by_dev.items():
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            tab = _EMU_TABLE.get(dev)
-            if tab is None or tab[0] != _EMU_EPOCH[0] or tab[1] != [k for k, _ in ents]:     # (a weight died: never read freed memory)
-                arr = (EmuPrepItem * len(ents))()
-                blk = 0
-                for i, (k, e) in enumerate(ents):
-                    _, ptr, N, K, ldw, tr = k
-                    arr[i].W, arr[i].image, arr[i].first_block = ptr, e[0].data_ptr(), blk
-                    arr[i].ldw, arr[i].N, arr[i].K, arr[i].transpose = ldw, N, K, int(tr)
-                    blk += lib().hoisdf_linear_emu_prepare_blocks(N, K, int(tr))
-                host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-                tab = (_EMU_EPOCH[0], [k for k, _ in ents], host.to(f"cuda:{dev}"), len(ents), blk)
-                _EMU_TABLE[dev] = tab
-            readers = set()
-            for _, e in ents:
-                readers |= e[5]
-            for s_ in readers:
-                if s_ != cur:
-                    cur.wait_stream(s_)      # every stream that read a previous image
-            call("hoisdf_linear_emu_prepare_batch", _p(tab[2]), tab[3], tab[4], _st())
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            for _, e in ents:
-                base = e[4]()
-                if base is None:
-                    continue
-                e[5].clear()
-                e[5].add(cur)                # the building stream: a rebuild from another stream has to wait for this build too
-                e[1], e[2], e[3] = (_WEIGHT_GEN[0], base._version), ev, cur
-
-
 def _emu_image(W: torch.Tensor, transpose: bool) -> torch.Tensor:
-    """the bf16x3 slab image of a weight (hoisdf_linear_emu_prepare), cached per (device, storage, shape, orientation) and
-    rebuilt in place when the weight changed (torch's version counter, or the generation FusedAdamW bumps).  The build is
-    recorded with an event: a consumer on another HIP stream (the object stack runs on a second one) waits for it, and is
-    remembered as a reader - a rebuild waits for every stream that read the previous image before overwriting it."""
-    from ._lib import lib
-    N, K = W.shape
-    key = (W.device.index, W.data_ptr(), N, K, W.stride(0), bool(transpose))
-    ver = (_WEIGHT_GEN[0], W._version)
-    cur = torch.cuda.current_stream(W.device)
-    ent = _EMU_IMAGES.get(key)
-    # the entry belongs to ONE tensor object (the parameter, or the parameter a slice views): another tensor that the
-    # allocator later placed at the same address must not hit it
-    base = W._base if W._base is not None else W
-    if ent is not None and ent[4]() is not base:
-        ent[1], ent[4] = None, __import__("weakref").ref(base)
-    if ent is None:
-        nb = lib().hoisdf_linear_emu_image_bytes(K if transpose else N, N if transpose else K)
-        ent = [torch.empty(nb, device=W.device, dtype=torch.uint8), None, None, None, __import__("weakref").ref(base), set()]
-        if len(_EMU_IMAGES) >= _EMU_PURGE_AT[0]:     # weights that came and went (tests): do not grow without bound
-            _emu_purge()
-            _EMU_PURGE_AT[0] = max(4096, 2 * len(_EMU_IMAGES))
-        _EMU_IMAGES[key] = ent
-        _EMU_EPOCH[0] += 1
-    if ent[1] != ver:
-        for s_ in ent[5]:
-            if s_ != cur:
-                cur.wait_stream(s_)          # every stream that read the previous image (the builder included)
-        ent[5].clear()
-        call("hoisdf_linear_emu_prepare", _p(W), W.stride(0), N, K, int(transpose), _p(ent[0]), _st())
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        ent[1], ent[2], ent[3] = ver, ev, cur
-    elif ent[3] != cur:
-        cur.wait_event(ent[2])
-    ent[5].add(cur)
-    return ent[0]
+    """the bf16x3 / f16x2 slab image of a weight (hoisdf_linear_emu_prepare) from the process's cache, current for this stream"""
+    return _EMU_CACHE.get(W, transpose, _WEIGHT_GEN[0])
 
 
 _H2 = [None]
@@ -449,7 +343,6 @@ _H2 = [None]
 def _h2() -> bool:
     """the process runs the f16x2 form of the emulated contractions (include/hoisdf.h, HOISDF_EMU_FORM)"""
     if _H2[0] is None:
-        from ._lib import lib
         _H2[0] = lib().hoisdf_linear_emu_pieces() == 2
     return _H2[0]
 
@@ -520,20 +413,17 @@ def _gemm_bwd_input(dy2, lddy, bits, p, W, dx, lddx, M, N, K, accumulate, dy_mag
     return None
 
 
-def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_scale=None, dy_scale=None, form=None, dy_mag=None, x_mag=None):
+def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_mag=None, dy_mag=None, form=None):
     """dW / db are zero-filled by the caller (the f32 kernel accumulates into them); the emulated form overwrites.
-    form "h2" / magnitude words given (x_scale / dy_scale: what _gemm_fwd / _gemm_bwd_input returned for the same operands):
+    form "h2" / magnitude words given (x_mag / dy_mag: what _gemm_fwd / _gemm_bwd_input returned for the same operands):
     hoisdf_linear_bwd_weight_emu_mag (f16x2 where the process runs that form; operands without words are measured by the library).
     No form and no magnitude words at hand: bf16x3, which needs none."""
-    x_mag = x_mag if x_mag is not None else x_scale
-    dy_mag = dy_mag if dy_mag is not None else dy_scale
     if _h2() and form != "b3":
         x_mag = x_mag if x_mag is not None else _mag_known(x2, ldx, M, K)
         dy_mag = dy_mag if dy_mag is not None else _mag_known(dy2, lddy, M, N)
     if (_GEMM_EMU and M >= _GEMM_EMU_DW_MIN_ROWS and min(N, K) >= _GEMM_EMU_DW_MIN_WIDTH and N % 4 == 0 and K % 4 == 0
             and lddy % 4 == 0 and ldx % 4 == 0 and dW.stride(0) == K and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
             and dW.data_ptr() % 16 == 0):
-        from ._lib import lib
         nws = lib().hoisdf_linear_bwd_weight_emu_workspace(M, N, K)
         ws = torch.empty(max(nws, 4), device=dW.device, dtype=torch.float32)
         if form == "h2" or dy_mag is not None or x_mag is not None:
@@ -551,7 +441,6 @@ def _gemm_bwd_weight(dy2, lddy, bits, p, x2, ldx, dW, db, M, N, K, x_scale=None,
         return
     ws, nws = None, 0
     if deterministic():             # partial tiles + ordered reduce instead of split-k atomics
-        from ._lib import lib
         nws = lib().hoisdf_linear_bwd_weight_workspace(M, N, K)
         ws = torch.empty(max(nws, 1), device=dW.device, dtype=torch.float32) if nws > 0 else None
     call("hoisdf_linear_bwd_weight", _p(dy2), lddy, _p(bits), float(p), _p(x2), ldx, _p(dW), dW.stride(0), _p(db), M, N, K,
@@ -572,7 +461,7 @@ class _Linear(torch.autograd.Function):
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         need_bits = bool(act) and (x.requires_grad or W.requires_grad or (b is not None and b.requires_grad))
         bits = torch.empty(M, (N + 31) // 32, device=x.device, dtype=torch.int32) if need_bits else None
-        ctx.x_scale = _gemm_fwd(x2, x2.stride(0) if M > 1 else K, W, b, y, N, M, N, K, act, drop_p, seed, bits)
+        ctx.x_mag = _gemm_fwd(x2, x2.stride(0) if M > 1 else K, W, b, y, N, M, N, K, act, drop_p, seed, bits)
         ctx.save_for_backward(x2, W, bits)
         ctx.meta = (int(act), float(drop_p), b is not None, x.shape)
         return y.view(*x.shape[:-1], N)
@@ -587,16 +476,16 @@ class _Linear(torch.autograd.Function):
         lddy = dy2.stride(0) if M > 1 else N
         # relu/dropout backward is fused into the staging of dy inside both contractions (1-bit sign map)
         p = drop_p if bits is not None else 0.0
-        dx = dW = db = dy_scale = None
+        dx = dW = db = dy_mag = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)
-            dy_scale = _gemm_bwd_input(dy2, lddy, bits, p, W, dx, K, M, N, K, 0)
+            dy_mag = _gemm_bwd_input(dy2, lddy, bits, p, W, dx, K, M, N, K, 0)
             dx = dx.view(xshape)
         if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
             buf = _zeros(N * K + (N if has_b else 0), dy.device)   # one fill (or a slice of the per-step arena)
             dW = buf[:N * K].view(N, K)
             db = buf[N * K:] if has_b else None
-            _gemm_bwd_weight(dy2, lddy, bits, p, x2, x2.stride(0) if M > 1 else K, dW, db, M, N, K, ctx.x_scale, dy_scale)
+            _gemm_bwd_weight(dy2, lddy, bits, p, x2, x2.stride(0) if M > 1 else K, dW, db, M, N, K, x_mag=ctx.x_mag, dy_mag=dy_mag)
         return dx, dW, db, None, None, None
 
 
@@ -707,7 +596,6 @@ class SdfQueryWeights:
 
     @torch.no_grad()
     def get(self):
-        from ._lib import SdfWeights, EmuPrepItem, lib
         ps = self._params()
         key = (_WEIGHT_GEN[0], _GEMM_EMU) + tuple((p.data_ptr(), p._version) for p in ps)
         if key == self._key:
@@ -751,17 +639,13 @@ class SdfQueryWeights:
             mats = [(keep[0], 512, Cc, Cc), (keep[2], 256, 512, 512), (keep[4], 512, 289, 289), (keep[6], 224, 512, 512),
                     (keep[8], 512, 516, 516), (keep[10], 512, 512, 512)]                # (W, N, K, ldw)
             if self._images is None:
-                imgs, arr, blk = [], (EmuPrepItem * 12)(), 0
+                imgs, items = [], []
                 for tr in (0, 1):
-                    for i, (W, N, K, ldw) in enumerate(mats):
+                    for W, N, K, ldw in mats:
                         nb = lib().hoisdf_linear_emu_image_bytes(K if tr else N, N if tr else K)
-                        img = torch.empty(nb, device=dev, dtype=torch.uint8)
-                        it = arr[6 * tr + i]
-                        it.W, it.image, it.first_block = W.data_ptr(), img.data_ptr(), blk
-                        it.ldw, it.N, it.K, it.transpose = ldw, N, K, tr
-                        blk += lib().hoisdf_linear_emu_prepare_blocks(N, K, tr)
-                        imgs.append(img)
-                table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+                        imgs.append(torch.empty(nb, device=dev, dtype=torch.uint8))
+                        items.append((W.data_ptr(), imgs[-1].data_ptr(), N, K, ldw, tr))
+                table, blk = prepare_batch_table(items, dev)
                 self._images = (imgs, table, blk, [m_[0].data_ptr() for m_ in mats])
             imgs, table, blk, ptrs = self._images
             assert ptrs == [m_[0].data_ptr() for m_ in mats]
@@ -777,7 +661,6 @@ def sdf_query(weights: SdfQueryWeights, pyr: "PyramidNHWC", points, center, cam_
               sample_idx=None, feat=None, want_feat=False, want_cam=False, drop_p: float = 0.0):
     """hoisdf_sdf_query_fwd: -> (sdf (n,), sdf_raw (n,), pe (n,30), cam (n,3) | None, feat (n,C) | None).
     ``feat``: rows already gathered for these camera points (shared gather); ``want_feat``: hand the gathered rows back."""
-    from ._lib import lib
     pts = points.reshape(-1, 3).contiguous()
     center, cam_intr = center.contiguous(), cam_intr.contiguous()
     _chk(pts, center, cam_intr, feat)
@@ -810,7 +693,6 @@ class _SdfQueryTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, points, center, cam_intr, scale, img_hw, clamp, drop_p, acc, wq, n_levels, *tensors):
-        from ._lib import lib
         levels, params = tensors[:n_levels], tensors[n_levels:]
         assert len(params) == 14
         pyr = PyramidNHWC(levels)
@@ -840,28 +722,18 @@ class _SdfQueryTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_sdf, _dpe, _dcam):
-        from ._lib import lib, SdfWeightGrads, _SDF_G
         pts, center, cam_intr, saved = ctx.saved_tensors
         w, _wq, scale, img_hw, clamp, drop_p, rps, shapes, B, acc, pshapes = ctx.meta
         dev = pts.device
         n, Cc = pts.shape[0], w.C
-        sizes = [512 * Cc, 512, 256 * 512, 256, 512 * 292, 512, 224 * 512, 224, 512 * 516, 512, 512 * 512, 512, 512, 1]
-        buf = _zeros(sum(sizes), dev)
-        parts, off = [], 0
-        for m in sizes:
-            parts.append(buf[off:off + m])
-            off += m
+        parts = _zero_views([512 * Cc, 512, 256 * 512, 256, 512 * 292, 512, 224 * 512, 224, 512 * 516, 512, 512 * 512, 512, 512, 1], dev)
         G = SdfWeightGrads(**{k: t.data_ptr() for k, t in zip(_SDF_G, parts)})
         if acc is not None:
             grads = acc.bufs
             acc.flat.record_stream(torch.cuda.current_stream(dev))
         else:
             grads = [torch.zeros(sh, device=dev, dtype=torch.float32) for sh in shapes]
-        g = Pyramid()
-        g.n_levels, g.B = len(grads), B
-        for i, t in enumerate(grads):
-            g.data[i] = t.data_ptr()
-            g.C[i], g.H[i], g.W[i] = t.shape[3], t.shape[1], t.shape[2]
+        g = _pyramid_struct(grads, B)
         n_ws = lib().hoisdf_sdf_query_train_workspace_bytes(n, Cc, 1)
         ws = torch.empty(n_ws, device=dev, dtype=torch.uint8)
         d_sdf = d_sdf.reshape(-1).contiguous()
@@ -891,7 +763,6 @@ _TOKENS_C = True                     # coarse K7 + K8 / K11 + K12 entries
 
 def sdf_query_train_ok() -> bool:
     """default arithmetic only, and not while bench.py brackets the individual calls (as _coarse_layer_ok)"""
-    from . import _lib
     return _SDF_QUERY_TRAIN_C and _lib._timer is None
 
 
@@ -1065,13 +936,19 @@ def token_build(tok, cam, center, pe, feat, sdf, beta, row0: int):
 # ---------------------------------------------------------------------------------------------
 # attention + layer norm
 # ---------------------------------------------------------------------------------------------
-def _attn_fwd(q, k, v, H, kv_len, drop_p, seed):
+def _attn_out(q, k, v, H, want_lse=True):
+    """checks that q (B,Lq,E), k, v (B,Lk,E) are row-uniform views -> (B, Lq, Lk, E, o (B,Lq,E), lse (B,H,Lq) | None), both uninitialised"""
     B, Lq, E = q.shape
     Lk = k.shape[1]
     for t, L in ((q, Lq), (k, Lk), (v, Lk)):
         assert t.stride(2) == 1 and t.stride(0) == L * t.stride(1), "attention operands must be row-uniform views"
     o = torch.empty(B, Lq, E, device=q.device, dtype=torch.float32)
-    lse = torch.empty(B, H, Lq, device=q.device, dtype=torch.float32)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=torch.float32) if want_lse else None
+    return B, Lq, Lk, E, o, lse
+
+
+def _attn_fwd(q, k, v, H, kv_len, drop_p, seed):
+    B, Lq, Lk, E, o, lse = _attn_out(q, k, v, H)
     call("hoisdf_attention_fwd", _p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(o), E, _p(lse),
          B, H, Lq, Lk, kv_len, float(drop_p), seed, _st())
     return o, lse
@@ -1103,26 +980,21 @@ def attention_emu() -> bool:
     return _ATTENTION_EMU
 
 
-def _use_split(Lq: int) -> int:
-    """attention kernel family for a call with Lq queries: 0 = exact-f32 MFMA, 2 = emulated fp32 (default; f16x2 when the caller
-    passes head magnitudes, else bf16x3; family 1, the split-precision training kernels of round 2, was retired in round 4).
-    The 17-query decoder attention keeps its own f32 kernels."""
-    if Lq < 32:
-        return 0
-    return 2 if _ATTENTION_EMU else 0
+def _attn_emulated(Lq: int) -> bool:
+    """does a call with Lq queries take the emulated fp32 kernels (default; f16x2 when the caller passes head magnitudes, else bf16x3)
+    or the exact-f32 MFMA ones?  The 17-query decoder attention keeps its own f32 kernels."""
+    return Lq >= 32 and _ATTENTION_EMU
 
 
 # forward workspaces whose Q / K / V planes the matching backward reuses (hoisdf_attention_fwd_emu(keep = 1) ->
 # hoisdf_attention_bwd_emu(fwd_workspace)): keyed by the operands' addresses - the autograd node keeps q, k, v alive until its
 # backward, so a key cannot be taken over by another live call; leftovers of graphs that never ran backward go at the next step /
 # at 64 entries.
+_EMU_PLANES = {}
 
 
 def _planes_key(q, k, v, H, kv_len):
     return (q.data_ptr(), k.data_ptr(), v.data_ptr(), tuple(q.shape), k.shape[1], H, kv_len)
-
-
-_EMU_PLANES = {}
 
 
 _ATTN_FORM_H2 = os.environ.get("HOISDF_ATTN_FORM", "h2")[:1].lower() != "b"
@@ -1136,15 +1008,9 @@ def _attn_h2(rows: int) -> bool:
 def _attn_fwd_emu(q, k, v, H, kv_len, drop_p, seed, keep=False, heads=None):
     """keep: a backward will follow - convert Q, K, V once into every plane it needs and park the workspace for it.
     heads = (q, k, v head magnitudes: one scale per (sample, head) and operand) -> the f16x2 form of the forward (no planes kept)"""
-    from ._lib import lib
-    B, Lq, E = q.shape
-    Lk = k.shape[1]
-    for t, L in ((q, Lq), (k, Lk), (v, Lk)):
-        assert t.stride(2) == 1 and t.stride(0) == L * t.stride(1), "attention operands must be row-uniform views"
+    B, Lq, Lk, E, o, lse = _attn_out(q, k, v, H)
     nbytes = lib().hoisdf_attention_emu_workspace(B, H, Lq, Lk, 2 if keep else 0)
     ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
-    o = torch.empty(B, Lq, E, device=q.device, dtype=torch.float32)
-    lse = torch.empty(B, H, Lq, device=q.device, dtype=torch.float32)
     if heads is not None:
         call("hoisdf_attention_fwd_emu_mag", _p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(o), E, _p(lse), B, H, Lq, Lk,
              kv_len, float(drop_p), seed, _p(ws), nbytes, 0, _p(heads[0]), _p(heads[1]), _p(heads[2]), None, _st())
@@ -1160,7 +1026,6 @@ def _attn_fwd_emu(q, k, v, H, kv_len, drop_p, seed, keep=False, heads=None):
 
 def _attn_bwd_emu(q, k, v, o, lse, do, dq, dk, dv, H, kv_len, drop_p, seed, heads=None):
     """heads: the (q, k, v) head magnitudes the forward used -> the f16x2 form of the backward"""
-    from ._lib import lib
     B, Lq, E = q.shape
     Lk = k.shape[1]
     assert dq.stride(1) == q.stride(1) and dk.stride(1) == k.stride(1) and dv.stride(1) == v.stride(1)
@@ -1191,16 +1056,16 @@ def _emu_bwd() -> bool:
     return _ATTN_BWD_EMU or deterministic()
 
 
-def _attn_fwd_mode(mode, q, k, v, H, kv_len, drop_p, seed, keep=False, heads=None):
-    if mode == 2 and heads is not None:
+def _attn_fwd_mode(emulated, q, k, v, H, kv_len, drop_p, seed, keep=False, heads=None):
+    if emulated and heads is not None:
         return _attn_fwd_emu(q, k, v, H, kv_len, drop_p, seed, heads=heads)
-    if mode == 2:
+    if emulated:
         return _attn_fwd_emu(q, k, v, H, kv_len, drop_p, seed, keep=keep and _emu_bwd())
     return _attn_fwd(q, k, v, H, kv_len, drop_p, seed)
 
 
-def _attn_bwd_mode(mode, *a, heads=None):
-    if mode == 2 and _emu_bwd():
+def _attn_bwd_mode(emulated, *a, heads=None):
+    if emulated and _emu_bwd():
         return _attn_bwd_emu(*a, heads=heads)
     return _attn_bwd(*a)
 
@@ -1213,20 +1078,20 @@ class _AttentionSelf(torch.autograd.Function):
         qkv = qkv.contiguous()
         _chk(qkv)
         E = qkv.shape[2] // 3
-        split = _use_split(qkv.shape[1])
-        o, lse = _attn_fwd_mode(split, qkv[:, :, :E], qkv[:, :, E:2 * E], qkv[:, :, 2 * E:], H, kv_len, drop_p, seed,
+        emulated = _attn_emulated(qkv.shape[1])
+        o, lse = _attn_fwd_mode(emulated, qkv[:, :, :E], qkv[:, :, E:2 * E], qkv[:, :, 2 * E:], H, kv_len, drop_p, seed,
                                 keep=any(ctx.needs_input_grad))
         ctx.save_for_backward(qkv, o, lse)
-        ctx.meta = (H, kv_len, float(drop_p), seed, split)
+        ctx.meta = (H, kv_len, float(drop_p), seed, emulated)
         return o
 
     @staticmethod
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
-        H, kv_len, drop_p, seed, split = ctx.meta
+        H, kv_len, drop_p, seed, emulated = ctx.meta
         E = qkv.shape[2] // 3
         d = torch.empty_like(qkv)
-        _attn_bwd_mode(split, qkv[:, :, :E], qkv[:, :, E:2 * E], qkv[:, :, 2 * E:], o, lse, do.contiguous(), d[:, :, :E],
+        _attn_bwd_mode(emulated, qkv[:, :, :E], qkv[:, :, E:2 * E], qkv[:, :, 2 * E:], o, lse, do.contiguous(), d[:, :, :E],
                        d[:, :, E:2 * E], d[:, :, 2 * E:], H, kv_len, drop_p, seed)
         return d, None, None, None, None
 
@@ -1239,20 +1104,20 @@ class _AttentionCross(torch.autograd.Function):
         q, kv = q.contiguous(), kv.contiguous()
         _chk(q, kv)
         E = q.shape[2]
-        split = _use_split(q.shape[1])
-        o, lse = _attn_fwd_mode(split, q, kv[:, :, :E], kv[:, :, E:], H, kv_len, drop_p, seed, keep=any(ctx.needs_input_grad))
+        emulated = _attn_emulated(q.shape[1])
+        o, lse = _attn_fwd_mode(emulated, q, kv[:, :, :E], kv[:, :, E:], H, kv_len, drop_p, seed, keep=any(ctx.needs_input_grad))
         ctx.save_for_backward(q, kv, o, lse)
-        ctx.meta = (H, kv_len, float(drop_p), seed, split)
+        ctx.meta = (H, kv_len, float(drop_p), seed, emulated)
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, kv, o, lse = ctx.saved_tensors
-        H, kv_len, drop_p, seed, split = ctx.meta
+        H, kv_len, drop_p, seed, emulated = ctx.meta
         E = q.shape[2]
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
-        _attn_bwd_mode(split, q, kv[:, :, :E], kv[:, :, E:], o, lse, do.contiguous(), dq, dkv[:, :, :E], dkv[:, :, E:], H, kv_len,
+        _attn_bwd_mode(emulated, q, kv[:, :, :E], kv[:, :, E:], o, lse, do.contiguous(), dq, dkv[:, :, :E], dkv[:, :, E:], H, kv_len,
                        drop_p, seed)
         return dq, dkv, None, None, None, None
 
@@ -1268,12 +1133,7 @@ def set_attention_f16_eval(on: bool) -> None:
 
 
 def _attn_fwd_f16(q, k, v, H, kv_len):
-    B, Lq, E = q.shape
-    Lk = k.shape[1]
-    for t, L in ((q, Lq), (k, Lk), (v, Lk)):
-        assert t.stride(2) == 1 and t.stride(0) == L * t.stride(1), "attention operands must be row-uniform views"
-    from ._lib import lib
-    o = torch.empty(B, Lq, E, device=q.device, dtype=torch.float32)
+    B, Lq, Lk, E, o, _ = _attn_out(q, k, v, H, want_lse=False)
     # bf16 hi + lo operands on the pipelined forward (hoisdf_attention_fwd_bf16x2)
     nbytes = lib().hoisdf_attention_bf16x2_workspace(B, H, Lq, Lk)
     ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
@@ -1455,7 +1315,7 @@ class _EncoderLayer(torch.autograd.Function):
         s_ln1 = next_seed() if p > 0 else 0
         s_ffn = next_seed() if p > 0 else 0
         s_ln2 = next_seed() if p > 0 else 0
-        split = _use_split(nq)
+        emulated = _attn_emulated(nq)
         if full:
             qkv, _ = _lin_fwd(x2d, w_in, b_in, False, 0.0, 0, False)
             qkv3 = qkv.view(B, S, 3 * E)
@@ -1473,7 +1333,7 @@ class _EncoderLayer(torch.autograd.Function):
             # gradient-free eval with cfg.attention_f16_eval: the f16-operand kernel (no LSE: nothing is saved for a backward)
             o, lse = _attn_fwd_f16(q, k, v, H, S), None
         else:
-            if split == 2 and _attn_h2(B * nq) and E == 64 * H:
+            if emulated and _attn_h2(B * nq) and E == 64 * H:
                 # the f16x2 form of the forward, as the coarse entry runs it: one scale per (sample, head) from the projected matrices
                 if full:
                     hm = _head_measure(qkv, 3 * E, B * S, 3 * H, S)
@@ -1481,7 +1341,7 @@ class _EncoderLayer(torch.autograd.Function):
                 else:
                     hq, hkv = _head_measure(qbuf, E, B * nq, H, nq), _head_measure(kvbuf, 2 * E, B * S, 2 * H, S)
                     heads = (hq, hkv, hkv[H * B:])
-            o, lse = _attn_fwd_mode(split, q, k, v, H, S, p, s_attn, keep=any(ctx.needs_input_grad), heads=heads)
+            o, lse = _attn_fwd_mode(emulated, q, k, v, H, S, p, s_attn, keep=any(ctx.needs_input_grad), heads=heads)
         M = B * nq
         a, _ = _lin_fwd(o.view(M, E), w_out, b_out, False, 0.0, 0, False)
         xq2 = xq.view(M, E)
@@ -1505,25 +1365,19 @@ class _EncoderLayer(torch.autograd.Function):
                  _st())
         ctx.save_for_backward(x, qkv if full else qbuf, qkv if full else kvbuf, o, lse, a, x1, h, bits, f, x2, st, w_in,
                               w_out, w1, w2, g1, g2, g3)
-        ctx.meta = (B, S, E, nq, full, float(p), H, (s_attn, s_ln1, s_ffn, s_ln2), split, ni)
+        ctx.meta = (B, S, E, nq, full, float(p), H, (s_attn, s_ln1, s_ffn, s_ln2), emulated, ni)
         ctx.attn_heads = heads
         return x2.view(B, nq, E), y.view(B, ni, E)
 
     @staticmethod
     def backward(ctx, g_x2, g_y):
         (x, qs, ks, o, lse, a, x1, h, bits, f, x2, st, w_in, w_out, w1, w2, g1, g2, g3) = ctx.saved_tensors
-        B, S, E, nq, full, p, H, (s_attn, s_ln1, s_ffn, s_ln2), split, ni = ctx.meta
+        B, S, E, nq, full, p, H, (s_attn, s_ln1, s_ffn, s_ln2), emulated, ni = ctx.meta
         dev = x.device
         M, F = B * nq, w1.shape[0]
         # one zero-initialised slice for every parameter gradient of the layer
-        sizes = [3 * E * E, 3 * E, E * E, E, E, E, F * E, F, E * F, E, E, E, E, E]
-        buf = _zeros(sum(sizes), dev)
-        parts, off = [], 0
-        for n in sizes:
-            parts.append(buf[off:off + n])
-            off += n
-        dw_in, db_in, dw_out, db_out, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2, dg3, dbe3 = parts
-        dw_in, dw_out, dw1, dw2 = dw_in.view(3 * E, E), dw_out.view(E, E), dw1.view(F, E), dw2.view(E, F)
+        dw_in, db_in, dw_out, db_out, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2, dg3, dbe3 = _zero_views(
+            [(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E], dev)
         gx2 = None if g_x2 is None else g_x2.contiguous().view(M, E)
         dx2 = torch.empty(M, E, device=dev)
         if g_y is not None:
@@ -1554,7 +1408,7 @@ class _EncoderLayer(torch.autograd.Function):
         _lin_bwd_input(da, None, 0.0, w_out, do, False)
         _lin_bwd_weight(da, None, 0.0, o.view(M, E), dw_out, db_out)
         heads = ctx.attn_heads                                        # (the f16x2 forward's head magnitudes: the backward runs in the same form)
-        bwd = lambda *a_: _attn_bwd_mode(split, *a_, heads=heads)
+        bwd = lambda *a_: _attn_bwd_mode(emulated, *a_, heads=heads)
         do3 = do.view(B, nq, E)
         if full:
             qkv3 = qs.view(B, S, 3 * E)
@@ -1608,7 +1462,6 @@ class _EncoderLayerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n_query, p, H, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3, eps, n_inter=None):
-        from ._lib import lib, EncoderLayerDesc, EncoderLayerWeights
         x = x.contiguous()
         params = (w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3)
         _chk(x, *params)
@@ -1617,7 +1470,7 @@ class _EncoderLayerC(torch.autograd.Function):
         nq = S if (n_query is None or n_query >= S) else int(n_query)
         ni = nq if (n_inter is None or n_inter >= nq) else int(n_inter)
         d = EncoderLayerDesc(B=B, S=S, E=E, F=w1.shape[0], H=H, n_query=nq, n_inter=ni, eps=eps, drop_p=p,
-                             attention=2 if _use_split(nq) == 2 else 0, attention_bwd_emulated=int(_emu_bwd()),
+                             attention=2 if _attn_emulated(nq) else 0, attention_bwd_emulated=int(_emu_bwd()),
                              training=int(any(ctx.needs_input_grad)))
         for i in range(4):                                     # attention, after out-projection, FFN hidden, after the FFN
             d.seed[i] = next_seed() if p > 0 else 0
@@ -1647,18 +1500,13 @@ class _EncoderLayerC(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_x2, g_y):
-        from ._lib import lib, EncoderLayerWeights, EncoderLayerGrads
         x, x2, saved, *params = ctx.saved_tensors
         w_in, _, w_out, _, _, _, w1, _, w2 = params[:9]
         d = ctx.desc
         B, S, E, F, nq = d.B, d.S, d.E, d.F, d.n_query
         dev = x.device
-        sizes = [3 * E * E, 3 * E, E * E, E, E, E, F * E, F, E * F, E, E, E, E, E]     # one zero slice for all parameter gradients
-        buf = _zeros(sum(sizes), dev)
-        parts, off = [], 0
-        for n in sizes:
-            parts.append(buf[off:off + n])
-            off += n
+        # one zero slice for all parameter gradients
+        parts = _zero_views([(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E], dev)
         G = EncoderLayerGrads(**{"d" + n: t.data_ptr() for n, t in zip(_ENC_W_NAMES, parts)})
         w = EncoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_ENC_W_NAMES, params)})
         _EncoderLayerC._images(w, (w_in, w_out, w1, w2), True, B * nq, B * S, E, nq == S)
@@ -1670,9 +1518,7 @@ class _EncoderLayerC(torch.autograd.Function):
         gy = None if g_y is None else g_y.contiguous()
         call("hoisdf_encoder_layer_bwd", _p(x), _p(x2), C.addressof(w), dp, _p(saved), saved.numel(), _p(gx2), _p(gy), _p(dx),
              C.addressof(G), _p(ws), n_ws, _st())
-        shaped = [parts[0].view(3 * E, E), parts[1], parts[2].view(E, E), parts[3], parts[4], parts[5], parts[6].view(F, E), parts[7],
-                  parts[8].view(E, F)] + parts[9:]
-        return (dx, None, None, None, *shaped, None, None)
+        return (dx, None, None, None, *parts, None, None)
 
 
 _ENC_W_NAMES = ("w_in", "b_in", "w_out", "b_out", "g1", "be1", "w1", "b1", "w2", "b2", "g2", "be2", "g3", "be3")
@@ -1680,9 +1526,8 @@ _ENCODER_LAYER_C = True              # tests set it to False to compare the C en
 
 
 def _coarse_layer_ok(p, x, *weights) -> bool:
-    """the C entry covers the default arithmetic; the opt-in split / f16 modes and bench.py's per-call event timing (which
+    """the C entry covers the default arithmetic; the opt-in f16 mode and bench.py's per-call event timing (which
     brackets the individual C-ABI calls from Python) take the op-by-op node"""
-    from . import _lib
     return _ENCODER_LAYER_C and _lib._timer is None and not _use_f16(p, x, *weights)
 
 
@@ -1700,7 +1545,6 @@ class _DecoderLayerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tgt, memory, query_pos, mask_u8, kv_len, p, H, eps, *params):
-        from ._lib import lib, DecoderLayerDesc, DecoderLayerWeights, _DEC_W
         tgt, memory, query_pos = tgt.contiguous(), memory.contiguous(), query_pos.contiguous()
         _chk(tgt, memory, query_pos, *params)
         assert len(params) == len(_DEC_W) and all(t.is_contiguous() for t in params) and mask_u8.dtype == torch.uint8
@@ -1730,18 +1574,11 @@ class _DecoderLayerC(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_y):
-        from ._lib import lib, DecoderLayerWeights, DecoderLayerGrads, _DEC_W
         tgt, memory, mask_u8, out, saved, *params = ctx.saved_tensors
         d = ctx.desc
         B, Q, S, E = d.B, d.Q, d.S, d.E
         dev = tgt.device
-        sizes = [t.numel() for t in params]
-        buf = _zeros(sum(sizes) + Q * E, dev)                     # one zero slice: every parameter gradient + d query_pos
-        parts, off = [], 0
-        for t, n in zip(params, sizes):
-            parts.append(buf[off:off + n].view(t.shape))
-            off += n
-        d_qpos = buf[off:off + Q * E].view(Q, E)
+        *parts, d_qpos = _zero_views([t.shape for t in params] + [(Q, E)], dev)      # one zero slice: every parameter gradient + d query_pos
         G = DecoderLayerGrads(**{"d" + n: t.data_ptr() for n, t in zip(_DEC_W, parts)})
         w = DecoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_DEC_W, params)})
         if _GEMM_EMU and B * S >= _GEMM_EMU_MIN_ROWS:
@@ -1763,7 +1600,6 @@ _DECODER_LAYER_C = True              # as _ENCODER_LAYER_C
 
 def decoder_layer_ok(p, *tensors) -> bool:
     """as _coarse_layer_ok: default arithmetic only, and not while bench.py brackets the individual calls"""
-    from . import _lib
     return _DECODER_LAYER_C and _lib._timer is None and not _use_f16(p, *tensors)
 
 
@@ -1849,7 +1685,6 @@ def vote_loss(off, cls, pts, gt_mm, radius: float):
 def _mlp_struct(weights, biases, act_last: bool, rows: int = 0, images: str = ""):
     """``images``: "f" -> the cached forward weight images ride along (hoisdf_mlp.img), "b" -> the transposed ones of the grad-input
     GEMMs (img_t), for chains over ``rows`` rows that take the emulated GEMM; the C side builds whatever is missing itself."""
-    from ._lib import Mlp, MLP_MAX_LAYERS
     n = len(weights)
     if not 1 <= n <= MLP_MAX_LAYERS:
         raise ValueError(f"an MLP of {n} layers does not fit hoisdf_mlp ({MLP_MAX_LAYERS})")
@@ -1879,18 +1714,12 @@ def _mlp_struct(weights, biases, act_last: bool, rows: int = 0, images: str = ""
 
 def _mlp_grads(weights, biases, device):
     """-> (hoisdf_mlp_grads, [dw..., db...] views of ONE zero-filled buffer from the step's arena)"""
-    from ._lib import MlpGrads
-    sizes = [w.numel() for w in weights] + [b.numel() for b in biases]
-    buf = _zeros(sum(sizes), device)
-    parts, off = [], 0
-    for n in sizes:
-        parts.append(buf[off:off + n])
-        off += n
-    G = MlpGrads()
     k = len(weights)
+    parts = _zero_views([w.shape for w in weights] + [b.numel() for b in biases], device)
+    G = MlpGrads()
     for i in range(k):
         G.dw[i], G.db[i] = parts[i].data_ptr(), parts[k + i].data_ptr()
-    return G, [parts[i].view_as(weights[i]) for i in range(k)], [parts[k + i] for i in range(k)]
+    return G, parts[:k], parts[k:]
 
 
 class _Tokens(torch.autograd.Function):
@@ -1943,8 +1772,7 @@ class _Tokens(torch.autograd.Function):
 
 
 def tokens_ok(*tensors) -> bool:
-    """the C entry covers the default arithmetic; bench.py's per-call event timing and the split mode take the op chain"""
-    from . import _lib
+    """the C entry covers the default arithmetic; bench.py's per-call event timing takes the op chain"""
     return _TOKENS_C and _lib._timer is None and all(t.is_cuda for t in tensors)
 
 
@@ -2055,7 +1883,6 @@ def mano_dirs_image(shapedirs, posedirs, weights):
     shapedirs, posedirs, weights = shapedirs.contiguous().float(), posedirs.contiguous().float(), weights.contiguous().float()
     _chk(shapedirs, posedirs, weights)
     assert shapedirs.shape == (778, 3, 10) and posedirs.shape == (778, 3, 135) and weights.shape == (778, 16)
-    from ._lib import lib
     image = torch.empty(lib().hoisdf_mano_dirs_image_floats(), device=shapedirs.device, dtype=torch.float32)
     call("hoisdf_mano_prepare", _p(shapedirs), _p(posedirs), _p(weights), _p(image), _st())
     return image
@@ -2166,8 +1993,6 @@ def aux_image_losses(decoder_out, joint_coord, hand_seg, obj_seg, sigma: float):
     return _AuxImageLosses.apply(decoder_out, joint_coord, hand_seg, obj_seg, sigma)
 
 
-
-
 # ---------------------------------------------------------------------------------------------
 # (f4) BatchNorm2d (+ residual) (+ ReLU) of a channels_last encoder map
 # ---------------------------------------------------------------------------------------------
@@ -2191,7 +2016,6 @@ _BN_WS = {}
 def _bn_workspace_floats(M: int, c: int) -> int:
     n = _BN_WS.get((M, c))
     if n is None:
-        from ._lib import lib
         n = _BN_WS[(M, c)] = lib().hoisdf_bn_workspace_floats(M, c)
     return n
 
@@ -2304,7 +2128,6 @@ def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr,
     """hoisdf_pose_infer: the eval forward of everything after the image encoder in ONE C-ABI call -> dict of the ``*_out`` tensors
     (with ``debug`` also the selected points and their SDF values).  Raises ValueError when a sample has fewer lattice survivors
     than requested points (nothing is launched then)."""
-    from ._lib import PoseOutputs
     d = prepared.desc
     dev = root.device
     if counts is None:

@@ -573,10 +573,67 @@ def test_batched_image_refresh_equals_the_single_builds():
         call("hoisdf_linear_emu_prepare", p(W), W.stride(0), N, K, int(tr), p(ref), st)
         assert torch.equal(img, ref), (tuple(W.shape), tr)
         assert O._emu_image(W, tr) is img                        # and the entry is current: no rebuild at the next use
-    n_before = len([k for k in O._EMU_IMAGES])
+    n_before = len(O._EMU_CACHE)
     y = O.linear(x, Ws[0])
     assert_close(y, x.double() @ Ws[0].double().t(), rel=2e-6, what="linear after the batched refresh")
-    assert len(O._EMU_IMAGES) == n_before
+    assert len(O._EMU_CACHE) == n_before
+
+
+def test_purge_keeps_live_images_and_drops_dead_ones():
+    """WeightImageCache.purge(): the entries of weights that died leave the cache, their images parked in the graveyard for one more
+    cycle (a kernel on another stream may still read them); the entries of live weights stay as they are - same image tensor, no
+    rebuild - and still serve the emulated linear layer."""
+    O = ops()
+    cache = O._EMU_CACHE
+    g = torch.Generator().manual_seed(11)
+    cache.purge()                                                 # (what earlier tests left behind is not counted below)
+    live = [(torch.randn(n, k, generator=g) / 8).to(DEV) for n, k in ((64, 64), (60, 256), (256, 64))]
+    imgs = [(W, tr, O._emu_image(W, tr)) for W in live for tr in (False, True)]
+    temps = [torch.randn(4 * i + 8, 64, generator=g).to(DEV) for i in range(8)]       # eight shapes: eight keys
+    dead = [O._emu_image(t, False) for t in temps]
+    n_before = len(cache)
+    del temps
+    cache.purge()
+    assert len(cache) == n_before - len(dead)
+    for W, tr, img in imgs:
+        assert O._emu_image(W, tr) is img, (tuple(W.shape), tr)
+    assert len(cache.graveyard) == len(dead) and all(a is b for a, b in zip(cache.graveyard, dead))
+    cache.purge()
+    assert cache.graveyard == [] and len(cache) == n_before - len(dead)
+    for W in live:
+        x = torch.randn(2048, W.shape[1], generator=g).to(DEV)
+        assert O._emu_ok(2048, x, W.shape[1], W.shape[1])
+        assert_close(O.linear(x, W), x.double() @ W.double().t(), rel=2e-6, what=f"linear after the purge {tuple(W.shape)}")
+
+
+def test_image_built_on_one_stream_is_safe_to_read_on_another():
+    """an image built late on a side stream is read on the current stream without any synchronisation by the caller (the cache's
+    build event), and rebuilt on the side stream after the current one read it and then changed the weight (the reader waits)."""
+    O = ops()
+    g = torch.Generator().manual_seed(12)
+    M, N, K = 2048, 64, 64
+    x = torch.randn(M, K, generator=g).to(DEV)
+    W = (torch.randn(N, K, generator=g) / 8).to(DEV)
+    ref = x.double() @ W.double().t()
+    a = torch.randn(4096, 4096, generator=g).to(DEV)
+    assert O._emu_ok(M, x, K, K)
+    cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    side.wait_stream(cur)                                         # the inputs were made on the current stream
+    with torch.cuda.stream(side):
+        b = a
+        for _ in range(6):
+            b = torch.matmul(b, a)                                # a few milliseconds ahead of the build: it finishes late
+        y_side = O.linear(x, W)
+    y = O.linear(x, W)                                            # no wait for the side stream here: the cache has to
+    assert_close(y, ref, rel=2e-6, what="read on the current stream")
+    W.mul_(2)
+    side.wait_stream(cur)                                         # as real callers do: the new weight values
+    with torch.cuda.stream(side):
+        y2 = O.linear(x, W)
+    cur.wait_stream(side)
+    assert_close(y_side, ref, rel=2e-6, what="built on the side stream")
+    assert_close(y2, 2 * ref, rel=2e-6, what="rebuilt on the side stream")
+    assert_close(y2, 2 * y.double(), rel=2e-6, what="twice the first")
 
 
 def _ref_attn64(q, k, v, H, kv=None):
