@@ -208,6 +208,67 @@ def synthetic_batch(B: int, n_hand: int, n_obj: int, seed: int = 1234):
     return inputs, targets, meta
 
 
+# ---- asymmetric geometry: every symmetry of synthetic_batch / synthetic_pyramid broken on purpose -------------------------------
+# (C, H, W) per level.  "encoder-like": the CNN decoder's channels (sum 992) on a 192 x 320 image's strides - ragged 16 x 16 tiles at
+# 24 x 40 and 12 x 20, both coarse LDS groups (240 and 60 pixels); x 4 channels: C / 4 > 256, the looping forward gather.
+# "odd": H > W, odd sizes, a level of two float4 columns, a level whose channels are no multiple of 64 (stays on the atomic path).
+PYRAMID_ENCODER_LIKE = ((32, 96, 160), (64, 48, 80), (128, 24, 40), (256, 12, 20), (512, 6, 10))
+PYRAMID_ENCODER_LIKE_BIG = tuple((4 * c, h, w) for c, h, w in PYRAMID_ENCODER_LIKE)
+PYRAMID_ODD = ((8, 37, 21), (64, 17, 33), (192, 5, 9))
+LEVEL_NAMES = ("stride2", "stride4", "stride8", "stride16", "stride32")
+
+_ASYM_THETA_DEG = (17.0, -31.0, 8.0, -12.0, 26.0, -5.0, 21.0, -23.0)
+# boxes as fractions (x0, y0, x1, y1) of (W, H, W, H): [60, 30, 260, 150], [20, 50, 200, 180], [100, 10, 300, 120] on 192 x 320
+_ASYM_BOX = ((0.1875, 0.15625, 0.8125, 0.78125), (0.0625, 0.2604167, 0.625, 0.9375), (0.3125, 0.0520833, 0.9375, 0.625),
+             (0.125, 0.1, 0.7, 0.9))
+_ASYM_CENTER = ((0.01, -0.02, 0.70), (-0.03, 0.01, 0.62), (0.02, 0.03, 0.81), (-0.01, -0.03, 0.66))
+
+
+def transposed(spec):
+    """the (C, H, W) levels of ``spec`` with H and W exchanged (the pyramid of the transposed image)"""
+    return tuple((c, w, h) for c, h, w in spec)
+
+
+def nonsquare_pyramid(B: int, spec=PYRAMID_ENCODER_LIKE, seed: int = 0, nonneg: bool = True) -> "OrderedDict[str, torch.Tensor]":
+    """Random NCHW feature maps with the (C, H, W) of ``spec`` per level, named like the CNN decoder's (stride2 ...)."""
+    out = OrderedDict()
+    for name, (c, h, w) in zip(LEVEL_NAMES, spec):
+        a = _rng("nspyr." + name, seed).standard_normal((B, c, h, w)).astype(np.float32)
+        out[name] = torch.from_numpy(np.maximum(a, 0) if nonneg else a)
+    return out
+
+
+def asymmetric_geometry(B: int, img_hw=(192, 320), seed: int = 77):
+    """``meta_info`` like synthetic_batch's, with nothing shared between samples or between the two image axes: per-sample
+    cam_intr = T_c R(theta_b) T_c^-1 K_b (the in-plane augmentation of data/dexycb.py:295,384: K = post_rot_trans . K; fx_b != fy_b
+    in 560-640, cx_b != cy_b, every K[0,1] and K[1,0] non-zero), per-sample boxes inside the H x W image, centres centimetres apart."""
+    H, W = img_hw
+    r = _rng("asym_geometry", seed)
+    ctr = ((W - 1) / 2.0, (H - 1) / 2.0)
+    K, boxes_h, boxes_o, root, ocen = [], [], [], [], []
+    for b in range(B):
+        lap = b // len(_ASYM_BOX)                               # samples beyond the tables: the tables again, shifted
+        fx, fy = 560.0 + 80.0 * r.random(), 560.0 + 80.0 * r.random()
+        if abs(fx - fy) < 8.0:
+            fy = fx - 24.0 if fx > 600.0 else fx + 24.0
+        cx, cy = ctr[0] + (0.02 + 0.03 * r.random()) * W, ctr[1] - (0.02 + 0.03 * r.random()) * H
+        th = np.deg2rad(_ASYM_THETA_DEG[b % len(_ASYM_THETA_DEG)] + 1.5 * lap)
+        Kb = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64)
+        R = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1]], np.float64)
+        Tc = np.array([[1, 0, ctr[0]], [0, 1, ctr[1]], [0, 0, 1]], np.float64)
+        K.append(Tc @ R @ np.linalg.inv(Tc) @ Kb)
+        x0, y0, x1, y1 = _ASYM_BOX[b % len(_ASYM_BOX)]
+        sh = 0.02 * lap
+        boxes_h.append([round((x0 + sh) * W), round((y0 + sh) * H), round((x1 - sh) * W), round((y1 - sh) * H)])
+        x0, y0, x1, y1 = _ASYM_BOX[(b + 1) % len(_ASYM_BOX)]
+        boxes_o.append([round((x0 + sh) * W) + 3, round((y0 + sh) * H) + 5, round((x1 - sh) * W) - 7, round((y1 - sh) * H) - 2])
+        c = np.array(_ASYM_CENTER[b % len(_ASYM_CENTER)]) + 0.004 * lap
+        root.append(c)
+        ocen.append(c + np.array([0.03, 0.02, 0.02]) * (1 + 0.5 * b) * (-1 if b % 2 else 1))
+    f32 = lambda a: torch.from_numpy(np.asarray(a, np.float64).astype(np.float32))
+    return dict(mano_root=f32(root), obj_center_cam=f32(ocen), cam_intr=f32(K), bbox_hand=f32(boxes_h), bbox_obj=f32(boxes_o))
+
+
 def synthetic_decoder_out(B: int, seed: int = 13):
     """a seeded stand-in for decoder_net's second output (B, 3, 128, 128): channel 0 = heat-map logits on the scale of the
     255-peaked target, channels 1 / 2 = segmentation probabilities in (0.01, 0.99) with a few saturated pixels (BCELoss

@@ -4,6 +4,7 @@ reference (/root/reference, read-only) on CPU.  Runs only in the build container
 reference never travels - only the arrays written here do.
 
 Usage:  python tests/golden/make_golden.py            (from the repo root)
+        python tests/golden/make_golden.py asym       (one group only: here g15, the other files stay untouched)
 
 Harness shims (none of them edits the reference):
   1. sys.path[0] = /root/reference, CWD = a scratch dir (config import mkdirs outputs/log);
@@ -481,6 +482,44 @@ def mano_golden():
     save("g9_mano", pose=pose, betas=betas, verts=v, joints=j, x6=x6, R=Rm, aa=aa, R_back=Rg)
 
 
+def asym_geometry_golden():
+    """g15: the reference itself on inputs without any of the symmetries the other fixtures share (hoisdf_amd.testing.
+    asymmetric_geometry: per-sample rotated intrinsics with fx != fy, cx != cy and non-zero off-diagonals, per-sample boxes and
+    centres) on a NON-SQUARE image: cfg.input_img_shape = (192, 320) and the 96 x 160 ... 6 x 10 "encoder-like" pyramid through the
+    _Decoder shim.  dexycb setting, B = 2, 48 + 16 points, bins 16.  Stored: sdf_forward of both fields (as g1),
+    get_input_transformer (as g4), sdf_infer of both fields with 24 / 8 points (as g3) and the eval outputs of Model.forward (what
+    the small g7 fixtures keep).  cfg.input_img_shape is restored afterwards."""
+    B, nh, no, hw = 2, 48, 16, (192, 320)
+    model, cfg = build_reference("dexycb", nh, no, 16)
+    keep_shape = cfg.input_img_shape
+    cfg.input_img_shape = hw
+    try:
+        model.eval()
+        pyr = T.nonsquare_pyramid(B, T.PYRAMID_ENCODER_LIKE, seed=15)
+        inputs, targets, _ = T.synthetic_batch(B, nh, no, seed=151)
+        meta = T.asymmetric_geometry(B, hw)
+        root, oc, K = meta["mano_root"], meta["obj_center_cam"], meta["cam_intr"]
+        out = {}
+        with torch.no_grad():
+            sh, _, peh = model.sdf_forward(pyr, inputs["hand_sdf_points"], root, K, cfg.hand_sdf_scale, "hand")
+            so, _, peo = model.sdf_forward(pyr, inputs["obj_sdf_points"], oc, K, cfg.obj_sdf_scale, "obj")
+            sf, _, _ = model.sdf_forward(pyr, inputs["hand_sdf_points"] * 6.0, root, K, cfg.hand_sdf_scale, "hand")
+            out.update({"g1.sdf_hand": sh, "g1.pe_hand": peh, "g1.sdf_obj": so, "g1.pe_obj": peo, "g1.sdf_far": sf})
+            fea, cam = model.get_input_transformer(pyr, inputs["hand_pre_points"], root, K, cfg.hand_sdf_scale)
+            out.update({"g4.fea": fea, "g4.cam": cam})
+            ph, sh, peh, _ = model.sdf_infer(pyr, root, K, meta["bbox_hand"], cfg.hand_sdf_scale, 24, "hand")
+            po, so, peo, _ = model.sdf_infer(pyr, oc, K, meta["bbox_obj"], cfg.obj_sdf_scale, 8, "obj")
+            out.update({"g3.pts_hand": ph, "g3.sdf_hand": sh, "g3.pe_hand": peh, "g3.pts_obj": po, "g3.sdf_obj": so, "g3.pe_obj": peo})
+            model.backbone_net, model.decoder_net = _Backbone(), _Decoder(pyr)
+            res = model(inputs, targets, meta, "eval")
+        out.update({"e2e." + k: v for k, v in res.items() if torch.is_tensor(v) and v.numel() < 200000
+                    and k not in ("hand_seg_gt_out", "obj_seg_gt_out", "hand_seg_pred_out", "obj_seg_pred_out", "joint_heatmap_out",
+                                  "joint_heatmap", "obj_seg", "hand_seg")})
+        save("g15_asym_geometry", **out)
+    finally:
+        cfg.input_img_shape = keep_shape
+
+
 def _stub_module(name, **attrs):
     m = types.ModuleType(name)
     for k, v in attrs.items():
@@ -659,3 +698,5 @@ if __name__ == "__main__":
         option_goldens()
     if "smallbeta" in which:
         smallbeta_goldens()
+    if "asym" in which:                 # (not in the default list: regenerating everything else is not needed for it)
+        asym_geometry_golden()

@@ -535,16 +535,18 @@ def test_fused_adamw_matches_torch_adamw():
     assert float(stock.state[gpu_p[0]]["step"]) == 5.0
 
 
-@pytest.mark.parametrize("channels_last", [False, True])
-def test_aux_image_losses_match_torch(channels_last):
-    """(f4) fused heat-map render + MSE + 2x BCE vs the torch formulation of main/model.py:128-143,404-422 (fwd + grad)."""
+@pytest.mark.parametrize("channels_last,H,W", [pytest.param(False, 128, 128, id="False"), pytest.param(True, 128, 128, id="True"),
+                                               pytest.param(False, 96, 160, id="False-96x160"), pytest.param(True, 96, 160, id="True-96x160")])
+def test_aux_image_losses_match_torch(channels_last, H, W):
+    """(f4) fused heat-map render + MSE + 2x BCE vs the torch formulation of main/model.py:128-143,404-422 (fwd + grad); 96 x 160:
+    H != W, the joints spread over the whole 160 x 96 extent (exchanging the map's sides moves every Gaussian)."""
     O = ops()
-    B, J, H, W, sigma = 3, 21, 128, 128, 1.25
+    B, J, sigma = 3, 21, 1.25
     g = torch.Generator().manual_seed(9)
     dec = torch.rand(B, 3, H, W, generator=g) * 0.98 + 0.01
     dec[:, 0] = dec[:, 0] * 300.0
     dec[0, 1, 0, 0], dec[0, 2, 0, 1] = 0.0, 1.0                       # saturated probabilities: clamped logs / 1e-12 floor
-    joints = torch.rand(B, J, 2, generator=g) * 128
+    joints = torch.rand(B, J, 2, generator=g) * torch.tensor([float(W), float(H)])
     hs = (torch.rand(B, H, W, generator=g) > 0.5).float()
     osg = (torch.rand(B, H, W, generator=g) > 0.5).float()
     w = [torch.rand(B, H, W, generator=g) for _ in range(3)]

@@ -388,3 +388,63 @@ def test_g14_sampler_fixture_is_the_references_selection():
             np.testing.assert_allclose(g[k + "hand_sdf_points"].numpy(), hand, atol=1e-6)
             if mode == "train":
                 np.testing.assert_allclose(g[k + "obj_pre_points"].numpy(), (d[2 * nh + no:, :3] - oc) * sc, atol=1e-6)
+
+
+def test_g15_asymmetric_geometry():
+    """The restatement against the reference itself where nothing is symmetric (tests/golden/make_golden.py asym_geometry_golden):
+    per-sample rotated intrinsics with fx != fy, cx != cy and non-zero off-diagonals, per-sample boxes and centres, a 192 x 320 image
+    and the 96 x 160 ... 6 x 10 pyramid.  Every other fixture has K = diag-symmetric copies on a square image, where reading K
+    transposed or exchanging the image sides changes nothing.  Bars: those of test_g1_sdf_forward, test_g3_sdf_infer,
+    test_g4_token_mlp and test_g7_e2e."""
+    g = load_golden("g15_asym_geometry")
+    hw = (192, 320)
+    Pm = T.det_params(T.hot_path_param_shapes(992))
+    pyr = T.nonsquare_pyramid(B, T.PYRAMID_ENCODER_LIKE, seed=15)
+    inputs, targets, _ = T.synthetic_batch(B, NH, NO, seed=151)
+    meta = T.asymmetric_geometry(B, hw)
+    root, oc, K = meta["mano_root"], meta["obj_center_cam"], meta["cam_intr"]
+    assert bool((K[:, 0, 1] != 0).all() and (K[:, 1, 0] != 0).all() and (K[0] != K[1]).any())          # the fixture's point
+    cfg = O.OracleCfg(num_samp_hand=NH, num_samp_obj=NO, bins_n=16, input_img_shape=hw)
+    with torch.no_grad():
+        # as g1
+        sh, peh = O.sdf_forward(Pm, cfg, pyr, inputs["hand_sdf_points"], root, K, 3.1, "hand")
+        so, peo = O.sdf_forward(Pm, cfg, pyr, inputs["obj_sdf_points"], oc, K, 3.1, "obj")
+        sf, _ = O.sdf_forward(Pm, cfg, pyr, inputs["hand_sdf_points"] * 6.0, root, K, 3.1, "hand")
+        close(sh, g["g1.sdf_hand"]); close(so, g["g1.sdf_obj"]); close(peh, g["g1.pe_hand"]); close(peo, g["g1.pe_obj"])
+        close(sf, g["g1.sdf_far"])
+        # as g4
+        fea, cam = O.token_mlp(Pm, cfg, pyr, inputs["hand_pre_points"], root, K, 3.1)
+        close(fea, g["g4.fea"]); close(cam, g["g4.cam"], atol=1e-6)
+        # as g3 (bins 16, 24 / 8 points)
+        ph, sh, peh = O.sdf_infer(Pm, cfg, pyr, root, K, meta["bbox_hand"], 3.1, 24, "hand")
+        po, so, peo = O.sdf_infer(Pm, cfg, pyr, oc, K, meta["bbox_obj"], 3.1, 8, "obj")
+        for a, b in ((ph, g["g3.pts_hand"]), (po, g["g3.pts_obj"])):
+            for i in range(a.shape[0]):
+                sa = {tuple(r) for r in a[i].numpy().round(6).tolist()}
+                sb = {tuple(r) for r in b[i].numpy().round(6).tolist()}
+                assert len(sa ^ sb) <= 2, len(sa ^ sb)
+        close(sh.abs().sum(1), g["g3.sdf_hand"].abs().sum(1), atol=1e-4)
+        close(so.abs().sum(1), g["g3.sdf_obj"].abs().sum(1), atol=1e-4)
+        close(peh.sum(1), g["g3.pe_hand"].sum(1), atol=2e-3)
+        # as g7
+        layer = MANO.ManoLayer(MANO.synthetic_assets(0))
+        out = O.hot_path_forward(Pm, cfg, pyr, inputs, targets, meta, "eval", mano_layer=layer, hands_mean=layer.th_hands_mean)
+    checked = 0
+    for k, ref in g.items():
+        if not k.startswith("e2e."):
+            continue
+        k = k[4:]
+        if k not in out:
+            raise AssertionError(f"oracle misses key {k}")
+        if k in ("obj_rot_out", "obj_trans_out"):      # per-point rows follow sort order: compare means
+            close(out[k].mean(1), ref.mean(1), atol=2e-5)
+        else:
+            tol = 1e-4 if ("loss" in k or k in ("obj_rot", "obj_trans")) else 2e-5
+            close(out[k], ref, atol=tol, rtol=2e-5)
+        checked += 1
+    assert checked >= 6
+    # the fixture tells a wrong geometry from a right one: the image sides exchanged moves the hand joints by far more than the bar
+    with torch.no_grad():
+        swapped = O.hot_path_forward(Pm, O.OracleCfg(num_samp_hand=NH, num_samp_obj=NO, bins_n=16, input_img_shape=hw[::-1]), pyr, inputs,
+                                     targets, meta, "eval", mano_layer=layer, hands_mean=layer.th_hands_mean)
+    assert float((swapped["hand_joints_out"] - g["e2e.hand_joints_out"]).abs().max()) > 1e-2
