@@ -142,6 +142,11 @@ class PoseWeights(C.Structure):
                 ("mano_v_template", C.c_void_p), ("mano_j_regressor", C.c_void_p), ("mano_hands_mean", C.c_void_p)]
 
 
+class EncoderDesc(C.Structure):
+    """include/hoisdf.h hoisdf_encoder_desc (the image encoder)"""
+    _fields_ = [("B", C.c_int), ("img_h", C.c_int), ("img_w", C.c_int), ("resnet_type", C.c_int), ("big_decoder", C.c_int)]
+
+
 _POSE_OUT = ("hand_joints_out", "obj_rot_out", "obj_trans_out", "mano_mesh_out", "mano_joints_out", "mano_shape_out",
              "hand_points_out", "obj_points_out", "hand_sdf_out", "obj_sdf_out")
 
@@ -241,6 +246,14 @@ SIGNATURES: Dict[str, List] = {
     "hoisdf_pose_prepare": [_P, _P, _P, _L, _P],
     "hoisdf_pose_infer_begin": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hoisdf_pose_infer": [_P, _P, _PYR, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
+    "hoisdf_conv_pack_weight": [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P],
+    "hoisdf_conv_plan": [_L, _I, _I, _I, _P, _P],
+    "hoisdf_conv2d_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "hoisdf_conv_transpose2d_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "hoisdf_maxpool2d_fwd": [_P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "hoisdf_encoder_prepare": [_P, _P, _I, _P, _L, _P],
+    "hoisdf_encoder_pyramid_shape": [_P, _PYR],
+    "hoisdf_encoder_infer": [_P, _P, _P, _P, _P, _P, _L, _P],
 }
 _RET = {"hoisdf_version": C.c_char_p, "hoisdf_last_error": C.c_char_p}
 _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I], None), "hoisdf_get_gemm_emu": ([], C.c_int), "hoisdf_get_deterministic": ([], C.c_int),
@@ -274,6 +287,14 @@ _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I]
           "hoisdf_attention_bf16x2_workspace": ([_I, _I, _I, _I], C.c_long),
           "hoisdf_attention_emu_workspace": ([_I, _I, _I, _I, _I], C.c_long),
           "hoisdf_attention_bwd_emu_workspace": ([_I, _I, _I, _I, _I], C.c_long),
+          "hoisdf_conv_packed_floats": ([_I, _I, _I, _I], C.c_long),
+          "hoisdf_conv_workspace_bytes": ([_L, _I, _I, _I], C.c_long),
+          "hoisdf_encoder_tensor_count": ([_P], C.c_int),
+          "hoisdf_encoder_tensor_name": ([_P, _I], C.c_char_p),
+          "hoisdf_encoder_tensor_numel": ([_P, _I], C.c_long),
+          "hoisdf_encoder_prepared_bytes": ([_P], C.c_long),
+          "hoisdf_encoder_infer_workspace": ([_P], C.c_long),
+          "hoisdf_encoder_launch_count": ([_P], C.c_int),
           "hoisdf_pose_prepared_bytes": ([_P], C.c_long),
           "hoisdf_pose_infer_workspace": ([_P, _P], C.c_long)}
 

@@ -43,6 +43,9 @@ class Config:
     # not in the reference: eval forwards run the stage after the image encoder through ONE C-ABI call (hoisdf_pose_infer) instead of
     # Model.hot_path's Python orchestration; same kernels, no losses in the output (HOISDF_INFER=native does the same)
     native_infer = False
+    # not in the reference: on that path (eval, no gradient, native_infer on) the image encoder too runs through the C ABI
+    # (hoisdf_encoder_infer: BatchNorm folded, exact-f32 HIP convolutions) instead of torch / MIOpen (HOISDF_ENCODER=native does the same)
+    native_encoder = False
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

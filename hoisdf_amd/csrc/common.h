@@ -186,8 +186,25 @@ int add_layernorm_bwd_mag(const float* dy, const float* x, const float* r, const
                           const float* dx_add, float* dx, float* dr, float* dgamma, float* dbeta, long M, int D, float drop_p, uint64_t seed,
                           uint32_t* dx_mag, uint32_t* dr_mag, void* stream);
 
+// ---- conv.hip: the implicit-GEMM convolution forward, for the public unit entries and for encoder_infer.hip
+struct ConvProblem {
+  int B, H, W, C_in, C_out, KH, KW, stride, pad, act;      // act: 0 none, 1 ReLU, 2 sigmoid
+  int transposed;                                          // ConvTranspose2d(4, 2, 1): H x W is the INPUT map, the output is 2 H x 2 W
+};
+struct ConvPlan {
+  int tile;               // 64 or 128 (square output tile)
+  int splitk, k_per_split;
+  long workspace_bytes;   // partial tiles of a split contraction (0: not split)
+};
+ConvPlan conv_plan(long M, int N, int K, int ncls);
+int conv_launch(const ConvProblem& c, const float* x, int ldx, const float* w_packed, const float* bias, const float* residual, int ldr,
+                float* y, int ldy, int c_off, void* workspace, long workspace_bytes, hipStream_t st);
+int conv_pack_launch(const float* w, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
+                     float eps, int C_out, int C_in, int KH, int KW, int transposed, float* packed, float* bias_out, hipStream_t st);
+int maxpool_launch(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, hipStream_t st);
+
 bool deterministic_mode();
-bool gemm_emu_mode();             // hoisdf_set_gemm_emu: ... as fp32 emulated on the bf16 MFMA pipe (default on)
+bool gemm_emu_mode();            // hoisdf_set_gemm_emu: ... as fp32 emulated on the bf16 MFMA pipe (default on)
 struct DetScratch {
   float* part;          // [gridDim.x][ncols] partials
   unsigned* ticket;     // arrival counter, zero between launches

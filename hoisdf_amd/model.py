@@ -62,6 +62,8 @@ def get_manoshape_memory_mask(cfg=_global_cfg):
 _SDFQ_CACHE = weakref.WeakKeyDictionary()
 # per-model cache of the prepared blob of the whole-model C entry (ops.PosePrepared), keyed like the folds above
 _POSE_CACHE = weakref.WeakKeyDictionary()
+# the same for the image encoder's blob (ops.EncoderPrepared); created only when the native encoder is asked for
+_ENCODER_CACHE = weakref.WeakKeyDictionary()
 
 
 @dataclasses.dataclass
@@ -222,6 +224,9 @@ class Model(nn.Module):
         ent = _POSE_CACHE.get(self)
         if ent is not None:
             ent["key"] = None            # the next infer_native prepares again (the build counter keeps counting)
+        ent = _ENCODER_CACHE.get(self)
+        if ent is not None:
+            ent["key"] = None
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
@@ -588,6 +593,44 @@ class Model(nn.Module):
         return ops.PoseInferCounts(prepared.desc, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
                                    meta_info["bbox_obj"])
 
+    # ---- the image encoder through the C ABI (include/hoisdf.h hoisdf_encoder_infer; opt-in, evaluation only) -------------------
+    def native_encoder_enabled(self) -> bool:
+        """cfg.native_encoder (default False) or HOISDF_ENCODER=native; honoured only where _forward_native runs"""
+        return bool(getattr(self.cfg, "native_encoder", False)) or os.environ.get("HOISDF_ENCODER", "") == "native"
+
+    def _encoder_prepared(self, B, H, W, device):
+        """the encoder's prepared blob (BatchNorm folds from the running statistics, packed weights), rebuilt only when an encoder
+        parameter or BatchNorm buffer, the batch size or the image size changed"""
+        if self.backbone_net is None or self.decoder_net is None:
+            raise RuntimeError("encode_native needs a model built with its image encoder")
+        sd = {}
+        for prefix, net in (("backbone_net.", self.backbone_net), ("decoder_net.", self.decoder_net)):
+            for n, t in list(net.named_parameters()) + list(net.named_buffers()):
+                if t.is_floating_point():
+                    sd[prefix + n] = t
+        key = (B, H, W, str(device), ops._WEIGHT_GEN[0]) + tuple((t.data_ptr(), t._version) for t in sd.values())
+        ent = _ENCODER_CACHE.get(self)
+        if ent is None:
+            ent = _ENCODER_CACHE[self] = {"key": None, "prepared": None, "builds": 0}
+        if ent["key"] != key:
+            from ._lib import EncoderDesc
+            for m in list(self.backbone_net.modules()) + list(self.decoder_net.modules()):
+                if isinstance(m, nn.BatchNorm2d) and (m.eps != 1e-5 or m.running_mean is None):
+                    raise RuntimeError("encode_native folds BatchNorm2d with running statistics and eps = 1e-5")
+            desc = EncoderDesc(B=B, img_h=H, img_w=W, resnet_type=self.cfg.resnet_type, big_decoder=int(self.cfg.use_big_decoder))
+            ent["builds"] += 1
+            ent["prepared"] = ops.EncoderPrepared(desc, sd, device, ent["builds"])
+            ent["key"] = key
+        return ent["prepared"]
+
+    @torch.no_grad()
+    def encode_native(self, img, want_aux=True):
+        """backbone_net + decoder_net in evaluation mode through ONE C-ABI call (hoisdf_encoder_infer: exact-f32 HIP convolutions,
+        BatchNorm folded): ``img`` (B, 3, H, W) -> (PyramidNHWC, aux NHWC [B][H / 2][W / 2][3] or None).  Running statistics only."""
+        ops._chk(img)
+        prepared = self._encoder_prepared(img.shape[0], img.shape[2], img.shape[3], img.device)
+        return ops.encoder_infer(prepared, img, want_aux)
+
     def _set_arithmetic(self, f16_eval=None):
         """the configuration's arithmetic switches -> ops (``f16_eval`` None: that one is left alone - infer_native does not offer it)"""
         c = self.cfg
@@ -604,13 +647,18 @@ class Model(nn.Module):
                    obj_seg_gt_out=targets["obj_seg"], obj_seg_pred_out=decoder_out[:, 2])
 
     def _forward_native(self, inputs, targets, meta_info):
-        """eval forward with the switch on: the encoder in PyTorch, then infer_native; dexycb keeps its ground-truth MANO outputs"""
+        """eval forward with the switch on: the encoder in PyTorch (or, with cfg.native_encoder, through hoisdf_encoder_infer), then
+        infer_native; dexycb keeps its ground-truth MANO outputs"""
         c = self.cfg
         self._set_arithmetic()
         with torch.no_grad():
             counts = self.infer_native_begin(meta_info, self.linear_sdfin.layers[0].weight.shape[1])
-            img_feat, skips = self.backbone_net(inputs["img"])
-            feature_pyramid, decoder_out = self.decoder_net(img_feat, skips)
+            if self.native_encoder_enabled():
+                feature_pyramid, aux = self.encode_native(inputs["img"], want_aux=c.dataset == "dexycb")
+                decoder_out = None if aux is None else aux.permute(0, 3, 1, 2)
+            else:
+                img_feat, skips = self.backbone_net(inputs["img"])
+                feature_pyramid, decoder_out = self.decoder_net(img_feat, skips)
             out = self.infer_native(self._pyramid(feature_pyramid), meta_info, counts)
             if c.dataset == "dexycb":
                 if not c.use_inverse_kinematics:

@@ -2162,3 +2162,155 @@ def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr,
          _p(counts.counts), C.addressof(counts_h), C.addressof(o), _p(ws), nbytes,
          None if side_stream is None else C.c_void_p(side_stream.cuda_stream), _st())
     return out          # (the call returns with the current stream ordered behind the side stream's work: no record_stream needed)
+
+
+# ---------------------------------------------------------------------------------------------
+# convolution forward on channels-last maps (include/hoisdf.h hoisdf_conv*; csrc/conv.hip): exact f32, evaluation only
+# ---------------------------------------------------------------------------------------------
+CONV_ACT = {None: 0, "none": 0, "relu": 1, "sigmoid": 2}
+
+
+class ConvWeight:
+    """A convolution's weight packed once for the implicit-GEMM kernel (hoisdf_conv_pack_weight), an evaluation-mode BatchNorm folded
+    in when ``bn`` = (gamma, beta, running_mean, running_var, eps) is given.  ``w``: [C_out][C_in][KH][KW], or ConvTranspose2d's
+    [C_in][C_out][4][4] with ``transposed``."""
+
+    def __init__(self, w, bias=None, bn=None, transposed: bool = False):
+        g, be, mu, var, eps = bn if bn is not None else (None, None, None, None, 0.0)
+        ts = [t if t is None else t.detach().contiguous() for t in (w, bias, g, be, mu, var)]
+        _chk(*ts)
+        self.transposed = bool(transposed)
+        self.C_out, self.C_in = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+        self.KH, self.KW = w.shape[2], w.shape[3]
+        n = lib().hoisdf_conv_packed_floats(self.C_out, self.C_in, self.KH, self.KW)
+        self.packed = torch.empty(n, device=w.device, dtype=torch.float32)
+        self.bias = torch.empty((self.C_out + 3) // 4 * 4, device=w.device, dtype=torch.float32)
+        call("hoisdf_conv_pack_weight", *(_p(t) for t in ts), float(eps), self.C_out, self.C_in, self.KH, self.KW, int(self.transposed),
+             _p(self.packed), _p(self.bias), _st())
+
+
+def conv_plan(M: int, C_out: int, K: int, classes: int = 1):
+    """(tile, splitk) the convolution takes for M output rows, C_out columns and a contraction of K (classes = 4: transposed)"""
+    tile, splitk = C.c_int(0), C.c_int(0)
+    call("hoisdf_conv_plan", M, C_out, K, classes, C.addressof(tile), C.addressof(splitk))
+    return tile.value, splitk.value
+
+
+def _conv_ws(M, C_out, K, classes, device):
+    n = lib().hoisdf_conv_workspace_bytes(M, C_out, K, classes)
+    if n < 0:
+        raise ValueError(lib().hoisdf_last_error().decode())
+    return (torch.empty(n, device=device, dtype=torch.uint8) if n else None), n
+
+
+def _nhwc_slice(x):
+    """a channels-last map or a channel slice of one: [B][H][W][C] with unit channel stride and dense pixels -> row stride"""
+    B, H, W, Cc = x.shape
+    ld = x.stride(2)
+    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
+        raise ValueError("expected an NHWC map (or a channel slice of one) with dense pixels")
+    return ld
+
+
+@torch.no_grad()
+def conv2d_nhwc(x, w: ConvWeight, stride: int = 1, pad: int = 0, act=None, residual=None, out=None, c_off: int = 0):
+    """y = act(conv(x) + bias (+ residual)) on NHWC maps; ``x`` / ``residual`` / ``out`` may be channel slices of wider maps, or
+    ``out`` a wider map whose channels [c_off, c_off + C_out) are written.  ConvTranspose2d(4, 2, 1) when ``w`` was packed transposed."""
+    _chk(x, residual, out)
+    B, H, W, _ = x.shape
+    ldx = _nhwc_slice(x)
+    if w.transposed:
+        OH, OW, M, K, classes = 2 * H, 2 * W, B * H * W, 4 * w.C_in, 4
+    else:
+        OH, OW = (H + 2 * pad - w.KH) // stride + 1, (W + 2 * pad - w.KW) // stride + 1
+        M, K, classes = B * OH * OW, w.KH * w.KW * w.C_in, 1
+    if out is None:
+        out = torch.empty(B, OH, OW, w.C_out, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, OH, OW) or c_off < 0 or out.shape[3] < c_off + w.C_out or x.shape[3] != w.C_in:
+        raise ValueError(f"conv2d_nhwc: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit the weight")
+    ldy = _nhwc_slice(out)
+    ws, nws = _conv_ws(M, w.C_out, K, classes, x.device)
+    if w.transposed:
+        if residual is not None:
+            raise ValueError("the transposed convolution takes no residual")
+        call("hoisdf_conv_transpose2d_fwd", _p(x), ldx, _p(w.packed), _p(w.bias), _p(out), ldy, c_off, B, H, W, w.C_in, w.C_out, CONV_ACT[act],
+             _p(ws), nws, _st())
+    else:
+        ldr = 0 if residual is None else _nhwc_slice(residual)
+        call("hoisdf_conv2d_fwd", _p(x), ldx, _p(w.packed), _p(w.bias), _p(residual), ldr, _p(out), ldy, c_off, B, H, W, w.C_in, w.C_out, w.KH,
+             w.KW, stride, pad, CONV_ACT[act], _p(ws), nws, _st())
+    return out[..., c_off:c_off + w.C_out]
+
+
+@torch.no_grad()
+def maxpool2d_nhwc(x):
+    """MaxPool2d(3, 2, 1) of an NHWC map"""
+    _chk(x)
+    B, H, W, Cc = x.shape
+    y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, device=x.device, dtype=torch.float32)
+    call("hoisdf_maxpool2d_fwd", _p(x), _nhwc_slice(x), _p(y), Cc, B, H, W, Cc, _st())
+    return y
+
+
+# ---------------------------------------------------------------------------------------------
+# the image encoder in evaluation mode behind one C entry (include/hoisdf.h hoisdf_encoder_*; csrc/encoder_infer.hip)
+# ---------------------------------------------------------------------------------------------
+def encoder_tensor_table(desc):
+    """[(checkpoint key, numel)] in the order hoisdf_encoder_prepare takes the tensors"""
+    L, d = lib(), C.addressof(desc)
+    n = L.hoisdf_encoder_tensor_count(d)
+    if n < 0:
+        raise ValueError(L.hoisdf_last_error().decode())
+    return [(L.hoisdf_encoder_tensor_name(d, i).decode(), L.hoisdf_encoder_tensor_numel(d, i)) for i in range(n)]
+
+
+class EncoderPrepared:
+    """The prepared blob of hoisdf_encoder_prepare (BatchNorm folds + packed weights) for one (descriptor, weights) pair and the
+    workspace of its frames.  ``tensors``: checkpoint key -> tensor, for every key of the table."""
+
+    def __init__(self, desc, tensors, device, version: int = 0):
+        table = encoder_tensor_table(desc)
+        keep = []
+        for name, numel in table:
+            t = tensors[name].detach().float().contiguous()
+            if t.numel() != numel:
+                raise ValueError(f"{name}: {t.numel()} elements, the table has {numel}")
+            keep.append(t)
+        _chk(*keep)
+        nbytes = lib().hoisdf_encoder_prepared_bytes(C.addressof(desc))
+        nws = lib().hoisdf_encoder_infer_workspace(C.addressof(desc))
+        if nbytes < 0 or nws < 0:
+            raise ValueError(lib().hoisdf_last_error().decode())
+        self.desc, self.version = desc, version
+        self.blob = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        self.workspace = torch.empty(nws, device=device, dtype=torch.uint8)
+        ptrs = (C.c_void_p * len(keep))(*(t.data_ptr() for t in keep))
+        call("hoisdf_encoder_prepare", C.addressof(desc), ptrs, len(keep), _p(self.blob), nbytes, _st())
+        self.stream = torch.cuda.current_stream(device)
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+        shape = Pyramid()
+        call("hoisdf_encoder_pyramid_shape", C.addressof(desc), C.byref(shape))
+        self.level_shapes = [(desc.B, shape.H[i], shape.W[i], shape.C[i]) for i in range(shape.n_levels)]
+
+
+@torch.no_grad()
+def encoder_infer(prepared: EncoderPrepared, img, want_aux: bool = True):
+    """hoisdf_encoder_infer: ``img`` (B, 3, H, W) as the dataset yields it (a channels_last tensor is passed without a copy, anything
+    else through one permute-copy) -> (PyramidNHWC, aux NHWC [B][H / 2][W / 2][3] or None)"""
+    d = prepared.desc
+    if tuple(img.shape) != (d.B, 3, d.img_h, d.img_w):
+        raise ValueError(f"encoder_infer: image {tuple(img.shape)}, prepared for {(d.B, 3, d.img_h, d.img_w)}")
+    x = img.permute(0, 2, 3, 1)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    _chk(x)
+    dev = x.device
+    levels = [torch.empty(s, device=dev, dtype=torch.float32) for s in prepared.level_shapes]
+    aux = torch.empty(d.B, d.img_h // 2, d.img_w // 2, 3, device=dev, dtype=torch.float32) if want_aux else None
+    cur = torch.cuda.current_stream(dev)
+    if prepared.stream != cur:
+        cur.wait_event(prepared.event)
+    ptrs = (C.c_void_p * len(levels))(*(t.data_ptr() for t in levels))
+    call("hoisdf_encoder_infer", C.addressof(d), _p(prepared.blob), _p(x), ptrs, _p(aux), _p(prepared.workspace), prepared.workspace.numel(), _st())
+    return PyramidNHWC(levels), aux

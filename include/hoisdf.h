@@ -819,6 +819,64 @@ int hoisdf_pose_infer(const hoisdf_pose_desc* desc, const void* prepared, const 
                       const int32_t* counts_device, const int32_t* counts_host, const hoisdf_pose_outputs* outputs,
                       void* workspace, long workspace_bytes, void* side_stream, void* stream);
 
+/* ---- convolution forward on channels-last maps (csrc/conv.hip): exact f32, evaluation only ------------------------------------
+ * reference: torch.nn.functional.conv2d / conv_transpose2d / max_pool2d as common/nets/resnet.py and common/nets/layer.py use them.
+ * An implicit GEMM on the f32 MFMA pipe (bit-for-bit an fmaf chain): output row m = (b, oy, ox), contraction k = (ky, kx, ci).
+ * x: dense NHWC map [B][H][W][C_in] with a row stride ldx >= C_in (a channel slice of a wider map works).  Weights are packed once
+ * by hoisdf_conv_pack_weight (hoisdf_conv_packed_floats floats + a bias of C_out rounded up to 4 floats; packed 16-byte aligned),
+ * which also folds an evaluation-mode BatchNorm: gamma != NULL -> s = gamma / sqrt(var + eps) (f64, rounded once), w' = w s,
+ * b' = (conv_bias - mean) s + beta.  w is torch's [C_out][C_in][KH][KW], or with transposed = 1 ConvTranspose2d's [C_in][C_out][4][4].
+ * Epilogue: y[pixel][c_off + co] = act(acc + bias[co] (+ residual[pixel][co])), y row stride ldy >= c_off + C_out, residual row stride
+ * ldr; act 0 none / 1 ReLU / 2 sigmoid.  hoisdf_conv_transpose2d_fwd is ConvTranspose2d(4, 2, 1): x is [B][H][W][C_in], y the
+ * [B][2 H][2 W] map, computed as its four output-parity classes (2x2-tap convolutions, K = 4 C_in).
+ * A problem of few output tiles cuts K over workgroups (hoisdf_conv_plan: tile 64 / 128, splitk > 1) through partial tiles in the
+ * caller's workspace and an ordered reduce - no float atomics, two runs give the same bits; hoisdf_conv_workspace_bytes(M, C_out, K,
+ * classes) with M = output rows (B OH OW; transposed: B H W), K = KH KW C_in (transposed: 4 C_in), classes = 1 (transposed: 4).
+ * hoisdf_maxpool2d_fwd: MaxPool2d(3, 2, 1), y = [B][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]. */
+long hoisdf_conv_packed_floats(int C_out, int C_in, int KH, int KW);
+int hoisdf_conv_pack_weight(const float* w, const float* conv_bias, const float* gamma, const float* beta, const float* mean,
+                            const float* var, float eps, int C_out, int C_in, int KH, int KW, int transposed, float* packed,
+                            float* bias_out, void* stream);
+int hoisdf_conv_plan(long M, int C_out, int K, int classes, int* tile, int* splitk);
+long hoisdf_conv_workspace_bytes(long M, int C_out, int K, int classes);
+int hoisdf_conv2d_fwd(const float* x, int ldx, const float* w_packed, const float* bias, const float* residual, int ldr, float* y,
+                      int ldy, int c_off, int B, int H, int W, int C_in, int C_out, int KH, int KW, int stride, int pad, int act,
+                      void* workspace, long workspace_bytes, void* stream);
+int hoisdf_conv_transpose2d_fwd(const float* x, int ldx, const float* w_packed, const float* bias, float* y, int ldy, int c_off, int B,
+                                int H, int W, int C_in, int C_out, int act, void* workspace, long workspace_bytes, void* stream);
+int hoisdf_maxpool2d_fwd(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, void* stream);
+
+/* ---- the image encoder in evaluation mode: image -> feature pyramid (csrc/encoder_infer.hip) ---------------------------------
+ * reference: backbone_net + decoder_net of main/model.py:367-368 (common/nets/resnet.py, common/nets/module.py) under model.eval().
+ * Forward only, exact f32, running statistics only (no training-mode BatchNorm, no backward).  Together with the whole-model
+ * entries above: image + camera inputs in, joints / MANO mesh / object pose out, from a host with neither Python nor PyTorch.
+ *   tensor table: every floating-point entry of backbone_net.* / decoder_net.* in state_dict() order (no num_batches_tracked), by
+ *            checkpoint key, e.g. "backbone_net.resnet.layer1.0.conv1.weight"; a host maps a checkpoint by name.
+ *   once   : hoisdf_encoder_prepared_bytes -> allocate -> hoisdf_encoder_prepare(tensors in table order): folds every BatchNorm
+ *            (eps = 1e-5) into its convolution on the device and packs every weight.  The blob is self-contained.
+ *   frame  : hoisdf_encoder_infer only enqueues on `stream`: img_nhwc [B][img_h][img_w][3] -> the five dense NHWC level buffers
+ *            described by hoisdf_encoder_pyramid_shape (cfg.mutliscale_layers order: stride 2 .. 32; fill their pointers into the
+ *            shape and hoisdf_pose_infer takes it as it is) and, when aux_out != NULL, [B][img_h / 2][img_w / 2][3] = heat-map (raw),
+ *            hand and object segmentation (sigmoid).  prepared / workspace: 256-byte aligned device memory.
+ * Refused with HOISDF_ERR_INVALID: an unknown depth, big_decoder below ResNet-50, image sides that are not multiples of 32, null
+ * pointers, a short blob or workspace, n_tensors that is not the table's. */
+typedef struct hoisdf_encoder_desc {
+  int B, img_h, img_w;
+  int resnet_type;                 /* 18 | 34 | 50 | 101 | 152 */
+  int big_decoder;                 /* cfg.use_big_decoder (setting "ho3d"): 3968-channel pyramid, ResNet-50 and deeper */
+} hoisdf_encoder_desc;
+int hoisdf_encoder_tensor_count(const hoisdf_encoder_desc* desc);
+const char* hoisdf_encoder_tensor_name(const hoisdf_encoder_desc* desc, int i);
+long hoisdf_encoder_tensor_numel(const hoisdf_encoder_desc* desc, int i);
+long hoisdf_encoder_prepared_bytes(const hoisdf_encoder_desc* desc);
+int hoisdf_encoder_prepare(const hoisdf_encoder_desc* desc, const float* const* tensors, int n_tensors, void* prepared,
+                           long prepared_bytes, void* stream);
+long hoisdf_encoder_infer_workspace(const hoisdf_encoder_desc* desc);
+int hoisdf_encoder_launch_count(const hoisdf_encoder_desc* desc);      /* kernels one hoisdf_encoder_infer (with aux_out) enqueues */
+int hoisdf_encoder_pyramid_shape(const hoisdf_encoder_desc* desc, hoisdf_pyramid* shape_only);
+int hoisdf_encoder_infer(const hoisdf_encoder_desc* desc, const void* prepared, const float* img_nhwc, float* const* level_out,
+                         float* aux_out, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- (f4) auxiliary image losses of the encoder outputs ---------------------------------------------------
  * reference: main/model.py:128-143 (render_gaussian_heatmap) and :404-422 (MSELoss / BCELoss with reduction none).
  * dec = decoder_out (B, 3, H, W) [heat-map, hand seg, object seg] with element strides (sb, sc, sh, sw) - NCHW or

@@ -32,6 +32,8 @@ def parse_args():
     ap.add_argument("--out_dir", type=str, default=None, help="default: the checkpoint's directory, else outputs/result")
     ap.add_argument("--native-infer", action="store_true",
                     help="run everything after the image encoder through the one C entry hoisdf_pose_infer (cfg.native_infer)")
+    ap.add_argument("--native-encoder", action="store_true",
+                    help="with --native-infer: the image encoder too through the C ABI (hoisdf_encoder_infer, cfg.native_encoder)")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -44,6 +46,7 @@ def main():
     a = parse_args()
     cfg.apply_setting(a.setting)
     cfg.native_infer = bool(a.native_infer)
+    cfg.native_encoder = bool(a.native_encoder)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
