@@ -38,7 +38,7 @@ class Config:
     # not in the reference: BASELINE.json configs[4] ("fp16 MFMA attention"): f16-operand attention kernel for
     # gradient-free forward passes (mode != "train"); off = exact f32 everywhere (the parity configuration)
     attention_f16_eval = False
-    gemm_emu = None              # None: follow the library default (on; HOISDF_GEMM=f32 turns it off).  True / False: linear layers as fp32 emulated on the bf16 MFMA pipe (exact 3-way bf16 splits, 6 products; csrc/gemm_emu.hip) / the exact-f32 MFMA GEMM
+    gemm_emu = None              # None: follow the library default (on; HOISDF_GEMM=f32 turns it off).  True / False: linear layers as fp32 emulated on the bf16 MFMA pipe (exact 3-way bf16 splits, 6 products; csrc/gemm_emu*.hip) / the exact-f32 MFMA GEMM
     attention_emu = None         # the same for the attention forward (csrc/attention_emu.hip); HOISDF_ATTENTION=f32 turns the default off
     # not in the reference: eval forwards run the stage after the image encoder through ONE C-ABI call (hoisdf_pose_infer) instead of
     # Model.hot_path's Python orchestration; same kernels, no losses in the output (HOISDF_INFER=native does the same)

@@ -1,6 +1,6 @@
 // Small-M linear layers as fp32 emulated on the bf16 MFMA pipe (round 4): the 17-query decoder stack and the regression heads run
-// ~100 GEMMs of 544 x 256 x 256 (.. x 1024) per training step.  The tiled kernels (gemm.hip, gemm_emu.hip) cut such a problem
-// into a handful of 128- / 256-row tiles and take 12-30 us each - latency, not arithmetic.  Here one workgroup owns one 32 x 32
+// ~100 GEMMs of 544 x 256 x 256 (.. x 1024) per training step.  The tiled kernels (gemm.hip, gemm_emu_b3.hip, gemm_emu_h2.hip) cut such a
+// problem into a handful of 128- / 256-row tiles and take 12-30 us each - latency, not arithmetic.  Here one workgroup owns one 32 x 32
 // output tile and its four waves split the contraction; there is no LDS staging of operands and one barrier (the final add of the
 // four partial tiles, in wave order): the operands (a few hundred KB, L2-resident) are read straight in the fragment layout of
 // v_mfma_f32_32x32x16_bf16 (lane = row / column of the tile, 8 consecutive contraction indices per lane and 16-step), split into
@@ -8,22 +8,10 @@
 // wave 4 load -> split -> MFMA rounds long at K = 256.  Same contracts, epilogues (bias, ReLU, dropout, 1-bit sign map) and
 // arithmetic (exact three-way split of both operands, six products, f32 accumulation) as hoisdf_linear_*_emu; reference call
 // sites: common/nets/transformer.py:366-395 (decoder layer), common/nets/layer.py:168-201 (MLP).
-#include "common.h"
+#include "gemm_emu.h"      // vector types, MFB, SPLIT1
 
 namespace hoisdf {
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define MFB(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-#define SPLIT1(x, i)                             \
-  do {                                           \
-    const __bf16 a_ = (__bf16)(x);               \
-    const float r1_ = (x) - (float)a_;           \
-    const __bf16 b_ = (__bf16)r1_;               \
-    const float r2_ = r1_ - (float)b_;           \
-    p0[i] = a_; p1[i] = b_; p2[i] = (__bf16)r2_; \
-  } while (0)
 struct Frag { bf16x8 p[3]; };
 __device__ __forceinline__ Frag split8(const float (&e)[8]) {
   bf16x8 p0, p1, p2;

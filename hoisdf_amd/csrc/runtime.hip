@@ -27,7 +27,7 @@ int check_launch(const char* what) {
 }
 
 static int g_det = -1;          // -1: not decided yet (environment), 0 / 1
-static int g_gemm_emu = 1;      // ... as fp32 emulated on the bf16 pipe (gemm_emu.hip); default on, HOISDF_GEMM=f32 / the setter turn it off
+static int g_gemm_emu = 1;      // ... as fp32 emulated on the bf16 pipe (gemm_emu.hip: entries; gemm_emu_b3 / _h2 / _dw.hip: kernels); default on, HOISDF_GEMM=f32 / the setter turn it off
 
 bool gemm_emu_mode() {
   static int env = -1;

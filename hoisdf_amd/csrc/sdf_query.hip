@@ -10,7 +10,7 @@
 //     [h1 | x0] of common/nets/sdf_net.py:104-106 is the row itself - layer 2 contracts all 516 columns with a
 //     column-padded weight matrix (zeros under the pad columns);
 //   * the weight-norm fold of the four decoder layers is done once by the caller (cached across calls in eval mode).
-// The contractions run on the fp32-emulating bf16x3 kernel (gemm_emu.hip; default) or on gemm_f32_kernel (hoisdf_set_gemm_emu(0)): at ~1.7 kFLOP per byte of activations these layers are
+// The contractions run on the fp32-emulating kernels (gemm_emu_h2.hip / gemm_emu_b3.hip; default) or on gemm_f32_kernel (hoisdf_set_gemm_emu(0)): at ~1.7 kFLOP per byte of activations these layers are
 // MFMA-bound, and a monolithic kernel that keeps a point tile's 512-wide activations on-chip is limited to 64-row
 // tiles by the 160 KB LDS (64 x 512 x 4 B = 128 KB + weight slab), i.e. 30 FLOP per streamed weight byte and two waves
 // per SIMD - measured/estimated below the 105-120 TF the tiled GEMM reaches on these shapes.

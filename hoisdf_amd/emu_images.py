@@ -1,4 +1,4 @@
-"""Cache of the slab images the emulated GEMM reads its weights from (csrc/gemm_emu.hip, hoisdf_linear_emu_prepare): one image per
+"""Cache of the slab images the emulated GEMM reads its weights from (csrc/gemm_emu_b3.hip / gemm_emu_h2.hip, hoisdf_linear_emu_prepare): one image per
 (weight view, orientation), rebuilt in place when the weight changes, singly at the next use or all at once after an optimizer step.
 An image is built on one HIP stream and read on others (the object stack runs on a second one): every entry remembers the event of
 its build and the streams that read it since."""

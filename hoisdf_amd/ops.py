@@ -289,7 +289,7 @@ def project_gather(pyr: PyramidNHWC, points, center, cam_intr, scale, img_hw=(25
 # ---------------------------------------------------------------------------------------------
 # linear
 # ---------------------------------------------------------------------------------------------
-# ---- fp32 emulated on the bf16 MFMA pipe (csrc/gemm_emu.hip): forward / grad-input of the large linear layers ------------
+# ---- fp32 emulated on the bf16 MFMA pipe (csrc/gemm_emu.hip and its kernel units gemm_emu_b3 / _h2 / _dw.hip): forward / grad-input of the large linear layers ------------
 _GEMM_EMU = os.environ.get("HOISDF_GEMM", "emu") != "f32"
 _GEMM_EMU_MIN_ROWS = 2048            # below this a problem is a handful of tiles: latency-bound, stays on the f32 kernel
 _GEMM_EMU_DW_MIN_ROWS = 8192         # grad-weight: the contraction runs over the rows (>= 32 slabs per slice at 256 slices)

@@ -1,4 +1,4 @@
-"""-m gpu: the fp32-emulating linear kernels (csrc/gemm_emu.hip; default form "h2": two scaled f16 pieces per operand, three f16
+"""-m gpu: the fp32-emulating linear kernels (csrc/gemm_emu.hip and its kernel units gemm_emu_b3.hip / gemm_emu_h2.hip / gemm_emu_dw.hip; default form "h2": two scaled f16 pieces per operand, three f16
 MFMA products, f32 accumulation; form "b3", HOISDF_EMU_FORM=b3: exact three-way bf16 split, six products - this file runs its
 linear-layer tests under both, the second in a child process) are held to the bars of the exact-f32 MFMA kernel:
   * against fp64 at the exact kernel's tolerance (2e-6 of the tensor's max on rows spanning 8 decades, ragged shapes, ReLU +
@@ -48,7 +48,9 @@ def _emu_on():
 
 @pytest.mark.parametrize("M,N,K,act,p", [(4096, 512, 992, True, 0.0), (2500, 223, 292, True, 0.2), (2176, 128, 224, False, 0.0),
                                          (3000, 96, 516, True, 0.0), (2048, 768, 256, False, 0.0), (2049, 60, 256, False, 0.0),
-                                         (5000, 1024, 256, True, 0.1), (2304, 3, 256, True, 0.0), (2100, 256, 20, False, 0.0)])
+                                         (5000, 1024, 256, True, 0.1), (2304, 3, 256, True, 0.0), (2100, 256, 20, False, 0.0),
+                                         # masked grad-input over N >= 768 with a k tail on 208 tiles: emu_h2_kernel<true, true, 4>, the wide tile
+                                         (53248, 776, 256, True, 0.1)])
 def test_emulated_linear_matches_fp64_at_the_exact_kernels_bar(M, N, K, act, p):
     """forward, grad-input (plain and accumulating) through hoisdf_linear_fwd_emu / _bwd_input_emu, grad-weight through the f32
     kernel, against fp64 at 2e-6 of each tensor's max.  Rows of x and dy span 8 decades, all-zero rows, ragged M (row clamp),

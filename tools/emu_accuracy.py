@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Accuracy of the fp32-emulating linear kernels (csrc/gemm_emu.hip) next to the exact-f32 MFMA kernels and torch's fp32 GEMM
+"""Accuracy of the fp32-emulating linear kernels (csrc/gemm_emu_b3.hip, gemm_emu_h2.hip, gemm_emu_dw.hip) next to the exact-f32 MFMA kernels and torch's fp32 GEMM
 (rocBLAS / hipBLASLt) on identical inputs: element-wise |err vs fp64| / sum_k |a_k||b_k| (max and RMS), forward and
 grad-input orientation, several K and two input distributions."""
 import sys, os, math

@@ -17,6 +17,7 @@ their data allows:
   dQ(t - 2) partial sums -> HBM, staging of tile t + 2, loads of tile t + 3, this wave's dQ(t - 1) partial -> LDS
 Units of one family are ordered STAGE-major over element quads so that neighbours are independent.
     python tools/gen/attn_bwd4_phase.py > hoisdf_amd/csrc/attn_bwd4_phase.inc"""
+from phase_emit import header, macro
 import sys
 PROD = [(2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)]          # (A plane, B plane): small terms first
 # S = Q . K^T is accumulated in the FORWARD's order (attn_fwd2_phase.py FWD2_S: PROD over (K plane, Q plane) with A = K; here A = Q, so
@@ -137,9 +138,8 @@ def main():
         w = "; ".join(work[m])
         lines.append(f"    {mf[m]}; {w}; SB();" if w else f"    {mf[m]}; SB();")
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    print("// generated by tools/gen/attn_bwd4_phase.py - the pinned body of one query tile of emu_attn_bwd4_kernel (one MFMA + the work behind it)")
-    print("\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1])
+    print(header("attn_bwd4_phase.py", "the pinned body of one query tile of emu_attn_bwd4_kernel (one MFMA + the work behind it)"))
+    print(macro(lines))
     print("// modelled issue cycles of the other work per slot: max %d, mean %.1f, slots over %d: %d" % (max(load), sum(load) / 120.0, CAP, sum(1 for x in load if x > CAP)), file=sys.stderr)
     print(" ".join(str(x) for x in load), file=sys.stderr)
 

@@ -13,6 +13,7 @@ useful a-priori bound: five products per product in the two contractions that re
 The floating units (softmax, split, dropout decisions, exchange, staging) are placed by the load balancer of attn_bwd4_phase.py inside
 the windows their data allows.
     python tools/gen/attn_bwd4h_phase.py > hoisdf_amd/csrc/attn_bwd4h_phase.inc"""
+from phase_emit import header, macro
 import os
 import sys
 P2 = [(1, 0), (0, 1), (0, 0)]                                    # (A plane, B plane) of two-piece operands: small terms first
@@ -138,9 +139,8 @@ def main():
         w = "; ".join(work[m])
         lines.append(f"    {mf[m]}; {w}; SB();" if w else f"    {mf[m]}; SB();")
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    print("// generated by tools/gen/attn_bwd4h_phase.py - the pinned body of one query tile of emu_attn_bwd4h_kernel (one MFMA + the work behind it)")
-    print("\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1])
+    print(header("attn_bwd4h_phase.py", "the pinned body of one query tile of emu_attn_bwd4h_kernel (one MFMA + the work behind it)"))
+    print(macro(lines))
     print("// modelled issue cycles of the other work per slot: max %d, mean %.1f, slots over %d: %d" % (max(load), sum(load) / float(N), CAP, sum(1 for x in load if x > CAP)), file=sys.stderr)
     print(" ".join(str(x) for x in load), file=sys.stderr)
 

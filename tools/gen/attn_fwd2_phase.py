@@ -6,6 +6,7 @@
                        maximum of tile t + 1, its dropout decisions (8 hashes, DROP only), the staging writes of K(t + 2) / V(t + 1)
                        and the loads of K(t + 3) / V(t + 2) behind them.
 `python tools/gen/attn_fwd2_phase.py` prints attn_fwd2_phase.inc."""
+from phase_emit import header, macro
 PROD = [(2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)]          # (x plane, y plane): small terms first
 
 
@@ -14,8 +15,7 @@ def emit(name, params, slots):
     for m, w in slots:
         lines.append(f"    {m}; {w}; SB();" if w else f"    {m}; SB();")
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    return "\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1]
+    return macro(lines)
 
 
 def phase_s():
@@ -110,7 +110,7 @@ def phase_pv2():
 
 
 if __name__ == "__main__":
-    print("// generated by tools/gen/attn_fwd2_phase.py - the pinned half-iterations of emu_attn_fwd2_kernel (one MFMA + the units behind it)")
+    print(header("attn_fwd2_phase.py", "the pinned half-iterations of emu_attn_fwd2_kernel (one MFMA + the units behind it)"))
     print(phase_s())
     print(phase_pv())
     print("// two planes per operand (bf16 hi + lo, three products per product): the 16-bit-operand evaluation kernel of BASELINE configs[4]")

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Emits the DPHASE macro of emu_dw2_kernel (hoisdf_amd/csrc/gemm_emu.hip): the 96 MFMAs of a phase (second half of slab s - 1:
+"""Emits the DPHASE macro of emu_dw2_kernel (hoisdf_amd/csrc/gemm_emu_dw.hip): the 96 MFMAs of a phase (second half of slab s - 1:
 a1 b1, a1 b0, a2 b0 | first half of slab s: a0 b2, a0 b1, a0 b0; 4 x 4 blocks each), each followed by the units pinned behind it:
 the 24 fragment reads of slab s, the reload of the other patch register set (slab s + 2) and the conversion + LDS writes of slab
 s + 1 (four columns x (four row pairs x U1..U4 + three 16-byte writes)).  `python tools/gen/dw2_phase.py` prints the macro."""
+from phase_emit import header, macro
 import sys
 
 # B fragment sets: bP = y1 of slab s - 1, then y2 of slab s; bQ = y0 of slab s - 1, then y0 of slab s; bR = y1 of slab s (the next
@@ -48,10 +49,9 @@ def emit():
         if m in NOTE: l += f"   /* {NOTE[m]} */"
         lines.append(l)
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    return "\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1]
+    return macro(lines)
 
 
 if __name__ == "__main__":
-    print("// generated by tools/gen/dw2_phase.py - the slot table of emu_dw2_kernel's phase (one MFMA + the units pinned behind it)")
+    print(header("dw2_phase.py", "the slot table of emu_dw2_kernel's phase (one MFMA + the units pinned behind it)"))
     print(emit())

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Emits the DHPHASE macro of emu_dw2h_kernel (hoisdf_amd/csrc/gemm_emu.hip, the f16x2 grad-weight): the 48 MFMAs of a phase
+"""Emits the DHPHASE macro of emu_dw2h_kernel (hoisdf_amd/csrc/gemm_emu_dw.hip, the f16x2 grad-weight): the 48 MFMAs of a phase
 (hi hi of slab s - 1 | lo hi, hi lo of slab s; 4 x 4 blocks each), each followed by the units pinned behind it: the 16 fragment
 reads of slab s, the conversion + LDS writes of slab s + 1 (four columns x (four row pairs x (DU1, DU2) + two 16-byte writes)) and
 the reload of the patch registers for slab s + 2.
@@ -9,6 +9,7 @@ the reload of the patch registers for slab s + 2.
   slots 32-47  hi lo of slab s       A = aH, B = bL      aH re-read at 16-19 (last used by MFMA 15), bL at 20-23
 On exit aH / bN hold the hi pieces of slab s: the next phase is called with bC and bN exchanged.
     python tools/gen/dw2h_phase.py > hoisdf_amd/csrc/dw2h_phase.inc"""
+from phase_emit import header, macro
 
 
 def table():
@@ -50,10 +51,9 @@ def emit():
         if m in note: l += f"   /* {note[m]} */"
         lines.append(l)
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    return "\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1]
+    return macro(lines)
 
 
 if __name__ == "__main__":
-    print("// generated by tools/gen/dw2h_phase.py - the slot table of emu_dw2h_kernel's phase (one MFMA + the units pinned behind it)")
+    print(header("dw2h_phase.py", "the slot table of emu_dw2h_kernel's phase (one MFMA + the units pinned behind it)"))
     print(emit())

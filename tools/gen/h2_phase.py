@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Emits HPHASE (wave tile 128 x 128, 4 x 4 MFMA blocks: the 256 x 256 tile, one workgroup per CU) and HPHASE2 (wave tile 128 x 64,
 4 x 2 blocks: the 256 x 128 tile, two workgroups per CU), the pinned bodies of one slab phase of emu_h2_kernel
-(hoisdf_amd/csrc/gemm_emu.hip): three groups of 4 NJ v_mfma_f32_32x32x16_f16 (three products per slab), each MFMA followed by the
+(hoisdf_amd/csrc/gemm_emu_h2.hip): three groups of 4 NJ v_mfma_f32_32x32x16_f16 (three products per slab), each MFMA followed by the
 fragment reads / staging units pinned behind it.
 
   group 0  hi hi of slab s - 1   A = aH, B = bC      (fragments read before the barrier)
@@ -11,6 +11,7 @@ On exit aH / bN hold slab s: the next phase is called with bC and bN exchanged. 
 the activation tile -> scale, hi plane, residual, lo plane -> two 8-byte LDS writes each; NJ 16-byte pieces of the weight image)
 and the loads of slab s + 2 are spread over the MFMAs.
     python tools/gen/h2_phase.py > hoisdf_amd/csrc/h2_phase.inc"""
+from phase_emit import header, macro
 
 
 def table(nj):
@@ -57,11 +58,10 @@ def emit(nj, name):
         if m in note: l += f"   /* {note[m]} */"
         lines.append(l)
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    return "\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1]
+    return macro(lines)
 
 
 if __name__ == "__main__":
-    print("// generated by tools/gen/h2_phase.py - the slot tables of emu_h2_kernel's phase (one MFMA + the units pinned behind it)")
+    print(header("h2_phase.py", "the slot tables of emu_h2_kernel's phase (one MFMA + the units pinned behind it)"))
     print(emit(4, "HPHASE"))
     print(emit(2, "HPHASE2"))

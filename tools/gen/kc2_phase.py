@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Emits the PHASE macro of emu_kc2_kernel (hoisdf_amd/csrc/gemm_emu.hip) from a slot table: 48 MFMAs of a phase, each followed
+"""Emits the PHASE macro of emu_kc2_kernel (hoisdf_amd/csrc/gemm_emu_b3.hip) from a slot table: 48 MFMAs of a phase, each followed
 by the staging / fragment-read units pinned behind it.  `python tools/gen/kc2_phase.py <variant>` prints the macro; the shipped
 variant is pasted into the kernel (the table is easier to audit than 48 hand-written lines)."""
+from phase_emit import macro
 import sys
 
 # MFMA order of a phase: (A fragments, B fragments) x (i, j)
@@ -59,8 +60,7 @@ def emit(v):
         if m in NOTE: l += f"   /* {NOTE[m]} */"
         lines.append(l)
     lines.append("  } while (0)")
-    width = max(len(l) for l in lines) + 1
-    return "\n".join(l.ljust(width) + "\\" for l in lines[:-1]) + "\n" + lines[-1]
+    return macro(lines)
 
 
 if __name__ == "__main__":
