@@ -1,10 +1,26 @@
 // Shared declarations of the fp32-emulating attention kernels (attention_emu.hip: conversion pre-pass, forward, the backward's delta and
-// dQ reduce passes; attention_emu_bwd4.hip / attention_emu_bwd4h.hip: the backward in the bf16x3 / f16x2 form).
+// dQ reduce passes; attention_emu_bwd4.inc: the one-pass backward, compiled as attention_emu_bwd4.hip in the bf16x3 form and as
+// attention_emu_bwd4h.hip in the f16x2 form).
 #pragma once
 #include "common.h"
 
 namespace hoisdf {
 namespace emu_attn {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int D = 64;                                  // head width
+constexpr float LN2 = 0.6931471805599453f;
 
 struct EmuAttn {
   // planes (any may be null when a kernel does not use it): [p] = piece 0, 1, 2

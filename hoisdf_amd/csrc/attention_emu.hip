@@ -9,28 +9,17 @@
 //   pre-pass  : f32 head slices -> bf16 planes, row-major [bh][Lp][64] and (V only) transposed [bh][64][Lp] (Q pre-scaled by
 //               log2(e)/8: softmax in the log2 domain, the LSE convention of attention.hip)
 //   forward   : block = 128 queries (lane = query), streams 32-key tiles of K rows / V^T:  S^T = K.Q^T, O^T += V^T.P^T
-//   backward  : ONE pass, 5 GEMM-equivalents (attention_emu_bwd4.hip; the f16x2 form: attention_emu_bwd4h.hip): block = 128 keys
+//   backward  : ONE pass, 5 GEMM-equivalents (attention_emu_bwd4.inc, compiled as attention_emu_bwd4.hip / _bwd4h.hip): block = 128 keys
 //               (lane = key: K, V fragments and dK, dV accumulators in registers), streams 32-query tiles of Q / dO rows.  Its dQ
 //               contribution goes to a per-key-block partial buffer [kb][bh][q][64]; a reduce pass (here) sums the key blocks in
 //               order: no atomics anywhere, run-to-run identical.
 // The dropout mask is the same function of (seed, query, key) as in the f32 kernels.
-#include <stdlib.h>
-
 #include "attention_emu.h"
 
 namespace hoisdf {
-using emu_attn::EmuAttn;
-using emu_attn::emu_block;
+using namespace emu_attn;
 
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int D = 64;
 constexpr int RP = 72;              // bf16 per row of a row-major [32][64] tile in LDS (144 B)
 constexpr int TPH = 36;             // bf16 per row of a transposed [64][32] tile in LDS (72 B: conflict-free 8-byte reads)
 constexpr int ROWS_T = 32 * RP;     // bf16 per row-major plane tile
@@ -90,8 +79,6 @@ __device__ __forceinline__ bf16x8 frag_trn(const __bf16* tile, int row, int jj, 
 // F16 (the f16x2 form of the attention, round 5): TWO planes of f16 bits - hi = f16(x scale s), lo = f16(x scale s - hi) with s the
 // power of two that the head magnitude of the block's (sample, head) gives (round 6; common.h: mag[head * B + b] - a sample's
 // planes do not depend on the other samples of the batch); the third plane pointers are not touched.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <bool F16>
 __global__ __launch_bounds__(256) void emu_attn_convert_kernel(const float* __restrict__ src, int ld, int L, int Lp, int B, int H,
                                                                float scale, __bf16* __restrict__ r0, __bf16* __restrict__ r1,
@@ -171,8 +158,6 @@ __global__ __launch_bounds__(256) void emu_attn_convert_kernel(const float* __re
 // separately (K(t + 1) and V(t) are read while K(t + 2) and V(t + 1) are written): four __shared__ objects of 13.5 KB, one barrier
 // per tile.
 // ============================================================================================================================
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // NPL = planes per operand: 3 = fp32-equivalent (six products per product); 2 = bf16 hi + lo operands, three products - the 16-bit-operand
 // evaluation kernel of BASELINE configs[4] (hoisdf_attention_fwd_bf16x2; ~2^-17 relative operand error, f32 softmax and accumulation)
 // F16 (with NPL = 2): the f16x2 form - the planes hold f16 hi + lo pieces of Q sQ, K sK, V sV (the powers of two from the head
@@ -233,8 +218,6 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
   float mt = -INFINITY;
 #define KFRAG(KB, p, j) (*reinterpret_cast<const bf16x8*>(&(KB)[(p) * ROWS_T + c * RP + 16 * (j) + 8 * h]))
 #define VFRAG(VB, p, dt, jj) frag_trn((VB) + (p) * TRN_T, (dt) * 32 + c, jj, h)
-#define SB() __builtin_amdgcn_sched_barrier(0)
-#define PK_SUB(d, x, y) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(x), "v"(y))
 // ---- units of the S phase: scores 2 pr, 2 pr + 1 of tile t -> probabilities -> (dropout) -> three bf16 planes
 #define PE1(pr)                                                                                                        \
   do {                                                                                                                 \
@@ -304,68 +287,6 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
 #define STV(p) st_trn(vw + (p) * TRN_T, rv[p], tid)
 #define LDK(p) rk[p] = ld_rows(kp[p], (size_t)ktn * 32, tid)
 #define LDV(p) rv[p] = ld_trn(vp[p], a.Lkp, (size_t)vtn * 32, tid)
-#ifndef FWD2_ABL
-#define FWD2_ABL 0
-#endif
-#if FWD2_ABL & 1            /* ablation (timing only, wrong results): no softmax / split / hash arithmetic */
-#undef PE1
-#undef PE2
-#undef PE3
-#undef PE4
-#undef PE3B
-#undef PM
-#undef PH1
-#undef PH2
-#undef PH3
-#define PE1(pr) ((void)0)
-#define PE2(pr) ((void)0)
-#define PE3(pr) ((void)0)
-#define PE4(pr) ((void)0)
-#define PE3B(pr) ((void)0)
-#define PM(i) ((void)0)
-#define PH1(pr) ((void)0)
-#define PH2(pr) ((void)0)
-#define PH3(pr) ((void)0)
-#endif
-#if FWD2_ABL & 8            /* no exp / subtract */
-#undef PE1
-#define PE1(pr) do { e_[pr] = f32x2{s_cur[2 * (pr)], s_cur[2 * (pr) + 1]}; } while (0)
-#endif
-#if FWD2_ABL & 16           /* no split arithmetic (planes = raw bits) */
-#undef PE2
-#undef PE3
-#undef PE4
-#define PE2(pr) do { ps += e_[pr].x + e_[pr].y; w0[pr] = __builtin_bit_cast(uint32_t, e_[pr].x); } while (0)
-#define PE3(pr) do { w1[pr] = __builtin_bit_cast(uint32_t, e_[pr].y); } while (0)
-#define PE4(pr)                                                                                                        \
-  do {                                                                                                                 \
-    w2[pr] = w0[pr] ^ w1[pr];                                                                                          \
-    if (((pr) & 3) == 3) {                                                                                             \
-      pw[(pr) >> 2][0] = __builtin_bit_cast(bf16x8, u32x4{w0[(pr) - 3], w0[(pr) - 2], w0[(pr) - 1], w0[pr]});          \
-      pw[(pr) >> 2][1] = __builtin_bit_cast(bf16x8, u32x4{w1[(pr) - 3], w1[(pr) - 2], w1[(pr) - 1], w1[pr]});          \
-      pw[(pr) >> 2][2] = __builtin_bit_cast(bf16x8, u32x4{w2[(pr) - 3], w2[(pr) - 2], w2[(pr) - 1], w2[pr]});          \
-    }                                                                                                                  \
-  } while (0)
-#endif
-#if FWD2_ABL & 32           /* no running maximum */
-#undef PM
-#define PM(i) ((void)0)
-#endif
-#if FWD2_ABL & 2            /* no staging: the tiles of the prologue are re-read */
-#undef STK
-#undef STV
-#undef LDK
-#undef LDV
-#define STK(p) ((void)0)
-#define STV(p) ((void)0)
-#define LDK(p) ((void)0)
-#define LDV(p) ((void)0)
-#endif
-#if FWD2_ABL & 4            /* no barrier */
-#define FWD2_SYNC() ((void)0)
-#else
-#define FWD2_SYNC() __syncthreads()
-#endif
 #pragma push_macro("MB")
 #undef MB
 #define MB(a_, b_, c_)                                                                                                             \
@@ -448,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
     if constexpr (NPL == 3) FWD2_PV(VR); else FWD2_PV2(VR);                                                            \
     if ((t) + 1 <= lastt) FWD2_TILE_STATS((t) + 1, false);      /* (the re-read tile past the end is dropped) */          \
     s_cur = s_nxt;                                                                                                     \
-    FWD2_SYNC();                                                                                                       \
+    __syncthreads();                                                                                                     \
   } while (0)
   int t = 0;
   for (; t + 1 < ntiles; t += 2) {
@@ -458,8 +379,6 @@ __global__ __launch_bounds__(256, 2) void emu_attn_fwd2_kernel(EmuAttn a) {
   if (t < ntiles) FWD2_ITER(t, Kb1, Kb0, Vb0, Vb1);
 #undef KFRAG
 #undef VFRAG
-#undef SB
-#undef PK_SUB
 #undef PE1
 #undef PE2
 #undef PE3
@@ -565,13 +484,35 @@ namespace {
 inline long pad128(long L) { return (L + 127) / 128 * 128; }
 inline size_t plane_elems(int B, int H, long Lp) { return (size_t)B * H * Lp * 64; }
 
-// one tensor's planes inside a workspace: rows r[3] then transposed t[3] (either group may be absent)
+// one tensor's planes inside a workspace: npl row planes r[] then npl transposed planes t[] (either group may be absent)
 struct Planes { __bf16 *r[3], *t[3]; };
-inline Planes carve(__bf16*& w, size_t n, bool rows, bool trn) {
+inline Planes carve(__bf16*& w, size_t n, bool rows, bool trn, int npl = 3) {
   Planes p{};
-  for (int i = 0; i < 3; ++i) { p.r[i] = rows ? w : nullptr; if (rows) w += n; }
-  for (int i = 0; i < 3; ++i) { p.t[i] = trn ? w : nullptr; if (trn) w += n; }
+  for (int i = 0; i < npl; ++i) { p.r[i] = rows ? w : nullptr; if (rows) w += n; }
+  for (int i = 0; i < npl; ++i) { p.t[i] = trn ? w : nullptr; if (trn) w += n; }
   return p;
+}
+// THE layout of q, k, v planes (rows padded to 128): Q rows | K rows | [V rows] [V^T].  A forward workspace has V^T and, in its kept
+// form, the V rows (hoisdf_attention_emu_workspace); a backward that converts for itself has the V rows alone.
+struct QkvPlaneSet { Planes q, k, v; };
+inline QkvPlaneSet carve_qkv(__bf16*& w, int B, int H, int Lq, int Lk, bool v_rows, bool v_trn, int npl = 3) {
+  const size_t nq = plane_elems(B, H, pad128(Lq)), nk = plane_elems(B, H, pad128(Lk));
+  QkvPlaneSet s;
+  s.q = carve(w, nq, true, false, npl);
+  s.k = carve(w, nk, true, false, npl);
+  s.v = carve(w, nk, v_rows, v_trn, npl);
+  return s;
+}
+inline QkvPlaneSet fwd_planes(void* workspace, int B, int H, int Lq, int Lk, int keep) {
+  __bf16* w = reinterpret_cast<__bf16*>(workspace);
+  return carve_qkv(w, B, H, Lq, Lk, keep != 0, true);
+}
+// the fields every launch of the family fills the same way
+inline EmuAttn emu_args(int B, int H, int Lq, int Lk, int kv_len, float drop_p, uint64_t seed) {
+  EmuAttn a{};
+  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = (int)pad128(Lq); a.Lkp = (int)pad128(Lk); a.kv_len = kv_len;
+  a.drop_p = drop_p; a.inv_keep = 1.f / (1.f - drop_p); a.thresh = drop_threshold(drop_p); a.seed = seed;
+  return a;
 }
 // mag != null: the f16x2 planes (two planes, scaled per (sample, head) by the head magnitudes mag[head * B + b]); null: the bf16 planes
 int convert(const float* src, int ld, int L, int Lp, int B, int H, float scale, const Planes& p, hipStream_t st, const uint32_t* mag = nullptr) {
@@ -581,6 +522,13 @@ int convert(const float* src, int ld, int L, int Lp, int B, int H, float scale, 
   else hipLaunchKernelGGL(emu_attn_convert_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, st, src, ld, L, Lp, B, H, scale, p.r[0], p.r[1],
                           p.r[2], p.t[0], p.t[1], p.t[2], mag);
   return check_launch("attention_emu_convert");
+}
+// q (pre-scaled), k, v -> their planes; q_hm / k_hm / v_hm: the head magnitudes of the f16x2 form, or nulls
+int convert_qkv(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int H, int Lq, int Lk, const QkvPlaneSet& s,
+                hipStream_t st, const uint32_t* q_hm = nullptr, const uint32_t* k_hm = nullptr, const uint32_t* v_hm = nullptr) {
+  if (int rc = convert(q, ldq, Lq, (int)pad128(Lq), B, H, QS2, s.q, st, q_hm)) return rc;
+  if (int rc = convert(k, ldk, Lk, (int)pad128(Lk), B, H, 1.f, s.k, st, k_hm)) return rc;
+  return convert(v, ldv, Lk, (int)pad128(Lk), B, H, 1.f, s.v, st, v_hm);
 }
 int check_emu(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, int B, int H, int Lq, int Lk, int kv_len,
               float drop_p, const char* who) {
@@ -610,17 +558,10 @@ namespace {
 int fwd_over_planes(float* o, int ldo, float* lse, int B, int H, int Lq, int Lk, int kv_len, float drop_p, uint64_t seed,
                     void* workspace, int keep, hipStream_t st, uint32_t* o_mag, const uint32_t* q_hm = nullptr, const uint32_t* k_hm = nullptr,
                     const uint32_t* v_hm = nullptr) {
-  const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
-  __bf16* w = reinterpret_cast<__bf16*>(workspace);
-  const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
-  const Planes pq = carve(w, nq, true, false);
-  const Planes pk = carve(w, nk, true, false);
-  const Planes pv = carve(w, nk, keep != 0, true);
-  EmuAttn a{};
-  for (int i = 0; i < 3; ++i) { a.q[i] = pq.r[i]; a.k[i] = pk.r[i]; a.vt[i] = pv.t[i]; }
+  const QkvPlaneSet s = fwd_planes(workspace, B, H, Lq, Lk, keep);
+  EmuAttn a = emu_args(B, H, Lq, Lk, kv_len, drop_p, seed);
+  for (int i = 0; i < 3; ++i) { a.q[i] = s.q.r[i]; a.k[i] = s.k.r[i]; a.vt[i] = s.v.t[i]; }
   a.out = o; a.lse = lse; a.ldo = ldo; a.mag = o_mag; a.q_hm = q_hm; a.k_hm = k_hm; a.v_hm = v_hm;
-  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.kv_len = kv_len;
-  a.drop_p = drop_p; a.inv_keep = 1.f / (1.f - drop_p); a.thresh = drop_threshold(drop_p); a.seed = seed;
   const dim3 fgrid(cdiv(Lq, 128) * 8 * cdiv(B * H, 8));
   if (q_hm) {
     // (P is carried as 2^6 P up to 2^14 and the keep factor 1 / (1 - p) goes in before the f16 split: p < 0.75 keeps it below 65504)
@@ -660,16 +601,8 @@ int hoisdf::attention_fwd_emu_mag(const float* q, int ldq, const float* k, int l
   HOISDF_REQUIRE((!q_hm && !k_hm && !v_hm) || (q_hm && k_hm && v_hm), HOISDF_ERR_INVALID, "attention_fwd_emu: head magnitudes of all of q, k, v or of none");
   const long need = hoisdf_attention_emu_workspace(B, H, Lq, Lk, keep ? 2 : 0);
   HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_WORKSPACE, "attention_fwd_emu: workspace %ld < %ld bytes", workspace_bytes, need);
-  const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
   hipStream_t st = as_stream(stream);
-  __bf16* w = reinterpret_cast<__bf16*>(workspace);
-  const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
-  const Planes pq = carve(w, nq, true, false);
-  const Planes pk = carve(w, nk, true, false);
-  const Planes pv = carve(w, nk, keep != 0, true);
-  if (int rc = convert(q, ldq, Lq, Lqp, B, H, QS2, pq, st, q_hm)) return rc;
-  if (int rc = convert(k, ldk, Lk, Lkp, B, H, 1.f, pk, st, k_hm)) return rc;
-  if (int rc = convert(v, ldv, Lk, Lkp, B, H, 1.f, pv, st, v_hm)) return rc;
+  if (int rc = convert_qkv(q, ldq, k, ldk, v, ldv, B, H, Lq, Lk, fwd_planes(workspace, B, H, Lq, Lk, keep), st, q_hm, k_hm, v_hm)) return rc;
   return fwd_over_planes(o, ldo, lse, B, H, Lq, Lk, kv_len, drop_p, seed, workspace, keep, st, o_mag, q_hm, k_hm, v_hm);
 }
 
@@ -688,22 +621,13 @@ extern "C" int hoisdf_attention_fwd_bf16x2(const float* q, int ldq, const float*
                  HOISDF_ERR_INVALID, "attention_fwd_bf16x2: bad output / workspace");
   const long need = hoisdf_attention_bf16x2_workspace(B, H, Lq, Lk);
   HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_WORKSPACE, "attention_fwd_bf16x2: workspace %ld < %ld bytes", workspace_bytes, need);
-  const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
   hipStream_t st = as_stream(stream);
   __bf16* w = reinterpret_cast<__bf16*>(workspace);
-  const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
-  Planes pq{}, pk{}, pv{};
-  pq.r[0] = w; pq.r[1] = w + nq; w += 2 * nq;
-  pk.r[0] = w; pk.r[1] = w + nk; w += 2 * nk;
-  pv.t[0] = w; pv.t[1] = w + nk;
-  if (int rc = convert(q, ldq, Lq, Lqp, B, H, QS2, pq, st)) return rc;
-  if (int rc = convert(k, ldk, Lk, Lkp, B, H, 1.f, pk, st)) return rc;
-  if (int rc = convert(v, ldv, Lk, Lkp, B, H, 1.f, pv, st)) return rc;
-  EmuAttn a{};
-  for (int i = 0; i < 2; ++i) { a.q[i] = pq.r[i]; a.k[i] = pk.r[i]; a.vt[i] = pv.t[i]; }
+  const QkvPlaneSet s = carve_qkv(w, B, H, Lq, Lk, false, true, 2);       // the forward-only layout with two planes per operand
+  if (int rc = convert_qkv(q, ldq, k, ldk, v, ldv, B, H, Lq, Lk, s, st)) return rc;
+  EmuAttn a = emu_args(B, H, Lq, Lk, kv_len, 0.f, 0);
+  for (int i = 0; i < 2; ++i) { a.q[i] = s.q.r[i]; a.k[i] = s.k.r[i]; a.vt[i] = s.v.t[i]; }
   a.out = o; a.lse = nullptr; a.ldo = ldo;
-  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.kv_len = kv_len;
-  a.drop_p = 0.f; a.inv_keep = 1.f; a.thresh = 0; a.seed = 0;
   const dim3 fgrid(cdiv(Lq, 128) * 8 * cdiv(B * H, 8));
   hipLaunchKernelGGL((emu_attn_fwd2_kernel<false, 2, false>), fgrid, dim3(256), 0, st, a);
   return check_launch("attention_fwd_bf16x2");
@@ -712,19 +636,14 @@ extern "C" int hoisdf_attention_fwd_bf16x2(const float* q, int ldq, const float*
 // (internal, common.h) the plane addresses of a forward workspace as targets of linear_fwd_emu_qkv: q_part for a GEMM over the
 // B Lq query rows, kv_part for one over the B Lk memory rows (the same struct twice when Lq == Lk and one GEMM makes all three parts)
 void hoisdf::attention_emu_plane_targets(void* workspace, int B, int H, int Lq, int Lk, int keep, QkvPlanes& qp, QkvPlanes& kvp) {
-  const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
-  __bf16* w = reinterpret_cast<__bf16*>(workspace);
-  const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
-  const Planes pq = carve(w, nq, true, false);
-  const Planes pk = carve(w, nk, true, false);
-  const Planes pv = carve(w, nk, keep != 0, true);
+  const QkvPlaneSet s = fwd_planes(workspace, B, H, Lq, Lk, keep);
   qp = QkvPlanes{}; kvp = QkvPlanes{};
   qp.on = kvp.on = 1; qp.H = kvp.H = H; qp.E = kvp.E = H * 64; qp.qscale = kvp.qscale = QS2;
-  qp.L = Lq; qp.Lp = Lqp; kvp.L = Lk; kvp.Lp = Lkp;
+  qp.L = Lq; qp.Lp = (int)pad128(Lq); kvp.L = Lk; kvp.Lp = (int)pad128(Lk);
   for (int i = 0; i < 3; ++i) {
-    qp.r[0][i] = pq.r[i];
-    kvp.r[1][i] = pk.r[i]; kvp.r[2][i] = pv.r[i]; kvp.vt[i] = pv.t[i];
-    if (Lq == Lk) { kvp.r[0][i] = pq.r[i]; qp.r[1][i] = pk.r[i]; qp.r[2][i] = pv.r[i]; qp.vt[i] = pv.t[i]; }
+    qp.r[0][i] = s.q.r[i];
+    kvp.r[1][i] = s.k.r[i]; kvp.r[2][i] = s.v.r[i]; kvp.vt[i] = s.v.t[i];
+    if (Lq == Lk) { kvp.r[0][i] = s.q.r[i]; qp.r[1][i] = s.k.r[i]; qp.r[2][i] = s.v.r[i]; qp.vt[i] = s.v.t[i]; }
   }
 }
 
@@ -786,46 +705,33 @@ int hoisdf::attention_bwd_emu_mag(const float* q, int ldq, const float* k, int l
                  HOISDF_ERR_INVALID, "attention_bwd_emu: bad leading dims / alignment");
   const long need = hoisdf_attention_bwd_emu_workspace(B, H, Lq, Lk, fwd_workspace ? 1 : 0);
   HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_WORKSPACE, "attention_bwd_emu: workspace %ld < %ld bytes", workspace_bytes, need);
-  const int Lqp = (int)pad128(Lq), Lkp = (int)pad128(Lk);
   hipStream_t st = as_stream(stream);
-  const size_t nq = plane_elems(B, H, Lqp), nk = plane_elems(B, H, Lkp);
   __bf16* w = reinterpret_cast<__bf16*>(workspace);
-  const Planes pd = carve(w, nq, true, false);
+  const Planes pd = carve(w, plane_elems(B, H, pad128(Lq)), true, false);
   float* part = reinterpret_cast<float*>(w);
   w += (size_t)cdiv(Lk, 128) * B * H * Lq * 64 * 2;                 // (float = 2 bf16 slots)
-  Planes pq, pk, pv;
+  QkvPlaneSet s;
   if (fwd_workspace) {          // the planes hoisdf_attention_fwd_emu(keep = 1) left for the same q, k, v
     __bf16* f = reinterpret_cast<__bf16*>(const_cast<void*>(fwd_workspace));
-    pq = carve(f, nq, true, false); pk = carve(f, nk, true, false); pv = carve(f, nk, true, true);
+    s = carve_qkv(f, B, H, Lq, Lk, true, true);
   } else {
-    pq = carve(w, nq, true, false); pk = carve(w, nk, true, false); pv = carve(w, nk, true, false);
-    if (int rc = convert(q, ldq, Lq, Lqp, B, H, QS2, pq, st, q_hm)) return rc;
-    if (int rc = convert(k, ldk, Lk, Lkp, B, H, 1.f, pk, st, k_hm)) return rc;
-    if (int rc = convert(v, ldv, Lk, Lkp, B, H, 1.f, pv, st, v_hm)) return rc;
+    s = carve_qkv(w, B, H, Lq, Lk, true, false);
+    if (int rc = convert_qkv(q, ldq, k, ldk, v, ldv, B, H, Lq, Lk, s, st, q_hm, k_hm, v_hm)) return rc;
   }
-  if (int rc = convert(dout, lddo, Lq, Lqp, B, H, 1.f, pd, st, do_hm)) return rc;
+  if (int rc = convert(dout, lddo, Lq, (int)pad128(Lq), B, H, 1.f, pd, st, do_hm)) return rc;
   const long ng = (long)B * Lq * H;
   hipLaunchKernelGGL(emu_attn_delta_kernel, dim3((unsigned)((ng * 16 + 255) / 256)), dim3(256), 0, st, o, ldo, dout, lddo, delta, B, H, Lq);
   if (int rc = check_launch("attention_emu_delta")) return rc;
-  EmuAttn a{};
-  for (int i = 0; i < 3; ++i) {
-    a.q[i] = pq.r[i]; a.k[i] = pk.r[i]; a.v[i] = pv.r[i]; a.d[i] = pd.r[i];
-  }
+  EmuAttn a = emu_args(B, H, Lq, Lk, kv_len, drop_p, seed);
+  for (int i = 0; i < 3; ++i) { a.q[i] = s.q.r[i]; a.k[i] = s.k.r[i]; a.v[i] = s.v.r[i]; a.d[i] = pd.r[i]; }
   a.lse_in = lse; a.delta = delta; a.dq_part = part; a.dk = dk; a.dv = dv; a.ldk = ldk; a.ldv = ldv; a.mag = g_mag;
-  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.Lqp = Lqp; a.Lkp = Lkp; a.kv_len = kv_len;
-  a.drop_p = drop_p; a.inv_keep = 1.f / (1.f - drop_p); a.thresh = drop_threshold(drop_p); a.seed = seed;
   if (h2) {
     a.q_hm = q_hm; a.k_hm = k_hm; a.v_hm = v_hm; a.d_hm = do_hm;
     a.dq_scale = reinterpret_cast<float*>(pd.r[2]);          // (the third dO plane is free in this form: the reduce pass's B H factors live there)
-    if (int rc = attention_bwd4h_emu_launch(a, st)) return rc;
-    const long n4h = (long)B * H * Lq * 16;
-    hipLaunchKernelGGL(emu_attn_dq_reduce_kernel, dim3((unsigned)((n4h + 255) / 256)), dim3(256), 0, st, part, cdiv(kv_len, 128), dq, ldq,
-                       B, H, Lq, g_mag, (const float*)a.dq_scale);
-    return check_launch("attention_bwd_emu dq reduce");
   }
-  if (int rc = attention_bwd4_emu_launch(a, st)) return rc;
+  if (int rc = h2 ? attention_bwd4h_emu_launch(a, st) : attention_bwd4_emu_launch(a, st)) return rc;
   const long n4 = (long)B * H * Lq * 16;
   hipLaunchKernelGGL(emu_attn_dq_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, cdiv(kv_len, 128), dq, ldq,
-                     B, H, Lq, g_mag, (const float*)nullptr);
+                     B, H, Lq, g_mag, (const float*)(h2 ? a.dq_scale : nullptr));
   return check_launch("attention_bwd_emu dq reduce");
 }

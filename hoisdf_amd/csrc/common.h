@@ -239,6 +239,11 @@ __device__ __forceinline__ void block_column_sum(float* dstA, int nA, float* dst
   if (threadIdx.x == 0) *ds.ticket = 0u;
 }
 
+// ---- two pieces of text every hand-pinned main loop uses (the emulated GEMM and attention families): a fence the instruction
+// scheduler does not move anything across, and the packed f32 subtraction d = x - y (one VALU instruction for two values)
+#define SB() __builtin_amdgcn_sched_barrier(0)
+#define PK_SUB(d, x, y) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(x), "v"(y))
+
 // ---- wave-level reductions (64 lanes) -------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -90,10 +90,8 @@ __host__ __device__ __forceinline__ uint32_t* h2_trailer(void* image, int R, int
   }
 
 // ---- text the hand-pinned main loops share.  Macros, not functions: each kernel sees the tokens it would see with the text written
-// in place, so its schedule does not depend on what the inliner makes of a call.
+// in place, so its schedule does not depend on what the inliner makes of a call.  (SB() and PK_SUB: common.h.)
 #define NOP_ ((void)0)
-#define PK_SUB(d, a, b) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b))
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #define SYNC() do { SB(); __syncthreads(); SB(); } while (0)
 
 // Activation staging of emu_kc2_kernel and emu_h2_kernel (tile TM_ rows; MASK, KTAIL, g, m0, wave, wm, lane, l31, kh, last from the kernel).

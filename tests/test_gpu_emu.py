@@ -786,6 +786,38 @@ def test_f16x2_attention_backward_is_as_accurate_as_the_bf16x3_one(B, Lq, Lk, kv
         assert_close(dkvh, dkvb.double(), rel=5e-5, what="dkv with dropout")
 
 
+@pytest.mark.parametrize("B,Lq,Lk,kv,p", [(2, 300, 300, 230, 0.0), (1, 33, 160, 96, 0.1)])
+def test_bf16x3_backward_over_kept_planes_equals_converting_for_itself(B, Lq, Lk, kv, p):
+    """the two ways hoisdf_attention_bwd_emu finds its Q, K, V planes: in the workspace a forward with keep = 1 left (layout
+    Q rows | K rows | V rows | V^T, carved once in attention_emu.hip) or converted by itself (Q rows | K rows | V rows behind its dO
+    planes and dQ partials).  The same conversion kernel writes the same row planes both times, so dq and dkv are bit-equal; the kept
+    entry is consumed.  Shapes: ragged query and key tiles with masked keys; one full + one one-row query tile, a key block past
+    kv_len, dropout."""
+    O = ops()
+    import hoisdf_amd.ops as OO
+    E, H, seed = 256, 4, 1234
+    g = torch.Generator().manual_seed(Lq + Lk + 2)
+    q = torch.randn(B, Lq, E, generator=g).to(DEV)
+    kvm = torch.randn(B, Lk, 2 * E, generator=g).to(DEV)
+    go = torch.randn(B, Lq, E, generator=g).to(DEV)
+    k, v = kvm[..., :E], kvm[..., E:]
+    key = OO._planes_key(q, k, v, H, kv)
+
+    def run(keep):
+        o, lse = O._attn_fwd_emu(q, k, v, H, kv, p, seed, keep=keep)
+        assert (key in OO._EMU_PLANES) == keep
+        dq = torch.empty_like(q); dkv = torch.empty_like(kvm)
+        O._attn_bwd_emu(q, k, v, o, lse, go, dq, dkv[..., :E], dkv[..., E:], H, kv, p, seed)
+        assert key not in OO._EMU_PLANES                            # consumed
+        return o, dq, dkv
+    OO._EMU_PLANES.pop(key, None)
+    ok, dqk, dkvk = run(True)
+    oc, dqc, dkvc = run(False)
+    assert torch.equal(ok, oc)
+    assert torch.equal(dqk, dqc) and torch.equal(dkvk, dkvc)
+    assert float(dqk.abs().max()) > 0.0 and float(dkvk[:, :kv].abs().max()) > 0.0 and float(dkvk[:, kv:].abs().max()) == 0.0
+
+
 def test_emulated_attention_dropout_mask_is_the_f32_kernels_mask():
     """same (seed, query, key) hash as attention.hip: with dropout on, the emulated forward / backward agree with the exact-f32
     kernels to rounding (the SAME elements are dropped), and the backward is the adjoint of the forward in V (same mask)."""

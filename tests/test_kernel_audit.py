@@ -1,7 +1,7 @@
-"""The attention backward issues its MFMAs through inline asm (csrc/attention_emu_bwd4.hip: the operand register FILE is chosen per
-statement); hipcc pads no hazard around an asm statement, so every build is audited: no VALU write of an MFMA operand within two
-instructions ahead of the MFMA, every non-MFMA reader of an accumulator at least two MFMAs behind the chain's last product, no spills,
-no scratch.  hipcc cross-compiles for gfx950 without a GPU (about ten seconds)."""
+"""The attention backward issues its MFMAs through inline asm (csrc/attention_emu_bwd4.inc, compiled as attention_emu_bwd4.hip in the
+bf16x3 form and as attention_emu_bwd4h.hip in the f16x2 form: the operand register FILE is chosen per statement); hipcc pads no hazard
+around an asm statement, so every build is audited: no VALU write of an MFMA operand within two instructions ahead of the MFMA, every
+non-MFMA reader of an accumulator at least two MFMAs behind the chain's last product, no spills, no scratch.  hipcc cross-compiles for gfx950 without a GPU (about ten seconds)."""
 import os
 import re
 import shutil
@@ -38,7 +38,7 @@ def test_attention_backward_asm_mfma_hazard_audit(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_f16x2_attention_backward_asm_mfma_hazard_audit(tmp_path):
-    """the same audit for csrc/attention_emu_bwd4h.hip (76 MFMAs per query tile)"""
+    """the same audit for csrc/attention_emu_bwd4h.hip, the f16x2 form of the same text (76 MFMAs per query tile)"""
     src = os.path.join(ROOT, "hoisdf_amd", "csrc", "attention_emu_bwd4h.hip")
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-nonnull", "-c", src, "-o", str(tmp_path / "b4h.o"),
            "-save-temps=obj"]
@@ -48,6 +48,8 @@ def test_f16x2_attention_backward_asm_mfma_hazard_audit(tmp_path):
     assert asm, os.listdir(tmp_path)
     path = str(tmp_path / asm[0])
     text = open(path).read()
+    kernels = re.findall(r"\.name:\s+(_ZN6hoisdf21emu_attn_bwd4h_kernel\S+)", text)
+    assert len(set(kernels)) == 2, kernels                       # <DROP> x 2: every instantiation the library launches
     for m in re.finditer(r"\.name:\s+_ZN6hoisdf21emu_attn_bwd4h_kernel.*?\.vgpr_spill_count:\s+(\d+)", text, re.S):
         assert int(m.group(1)) == 0
     for m in re.finditer(r"\.name:\s+_ZN6hoisdf21emu_attn_bwd4h_kernel.*?\.private_segment_fixed_size:\s+(\d+)", text, re.S):
