@@ -8,6 +8,7 @@ No oracle import here (this module is part of the shipped package).
 """
 from __future__ import annotations
 
+import math
 import zlib
 from collections import OrderedDict
 from typing import Dict, Tuple
@@ -305,3 +306,142 @@ def to_device(tree, device):
     if torch.is_tensor(tree):
         return tree.to(device)
     return tree
+
+
+# ---- attention dropout held to fp64: the kernels print their own mask, autograd in float64 is the truth ---------------------------
+# A "kernel" here is a pair of callables on CPU tensors: fwd(q, k, v) -> o (B, Lq, E) and bwd(q, k, v, do) -> (dq, dk, dv), both under
+# one fixed (p, seed).  The dropout mask does not depend on the operand values, so one-hot V / dO read it out of them element by
+# element; nothing below knows the hash.  `valid` (broadcastable to (B, H, Lq, Lk), bool) marks the pairs that
+# take part in the softmax: keys below kv_len, pairs the uint8 mask leaves.  Every check raises AssertionError("<its name>: ...").
+ATTN_HEAD = 64
+
+
+def _one_hot_chunk(B: int, L: int, H: int, c: int) -> torch.Tensor:
+    """(B, L, H * 64) float32: 1 at [b, 64 c + d, h * 64 + d] for every b, h and d with 64 c + d < L, 0 elsewhere"""
+    t = torch.zeros(B, L, H, ATTN_HEAD)
+    d = torch.arange(min(ATTN_HEAD, L - ATTN_HEAD * c))
+    t[:, ATTN_HEAD * c + d, :, d] = 1.0
+    return t.view(B, L, H * ATTN_HEAD)
+
+
+def _heads(t: torch.Tensor, H: int) -> torch.Tensor:
+    return t.reshape(t.shape[0], t.shape[1], H, ATTN_HEAD).transpose(1, 2)
+
+
+def probe_dropped_probs_forward(fwd, q, k, H: int) -> torch.Tensor:
+    """Pd (B, H, Lq, Lk) float64 = the dropped, rescaled probability matrix of the forward: with V one-hot on chunk c of 64 keys,
+    o[b, i, h * 64 + d] = Pd[b, h, i, 64 c + d] - one non-zero term per output, so nothing is rounded"""
+    B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
+    pd = torch.zeros(B, H, Lq, Lk, dtype=torch.float64)
+    for c in range((Lk + ATTN_HEAD - 1) // ATTN_HEAD):
+        n = min(ATTN_HEAD, Lk - ATTN_HEAD * c)
+        o = fwd(q, k, _one_hot_chunk(B, Lk, H, c).to(q.dtype))
+        pd[..., ATTN_HEAD * c:ATTN_HEAD * c + n] = _heads(o.detach().cpu().double(), H)[..., :n]
+    return pd
+
+
+def probe_dropped_probs_backward(bwd, q, k, v, H: int) -> torch.Tensor:
+    """Pd (B, H, Lq, Lk) float64 as the backward regenerates it: dV = Pd^T dO needs neither delta nor dS, and with dO one-hot on
+    chunk c of 64 queries dv[b, j, h * 64 + d] = Pd[b, h, 64 c + d, j]"""
+    B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
+    pd = torch.zeros(B, H, Lq, Lk, dtype=torch.float64)
+    for c in range((Lq + ATTN_HEAD - 1) // ATTN_HEAD):
+        n = min(ATTN_HEAD, Lq - ATTN_HEAD * c)
+        dv = bwd(q, k, v, _one_hot_chunk(B, Lq, H, c).to(q.dtype))[2]
+        pd[:, :, ATTN_HEAD * c:ATTN_HEAD * c + n, :] = _heads(dv.detach().cpu().double(), H).transpose(-1, -2)[:, :, :n, :]
+    return pd
+
+
+def reference_probs(q, k, H: int, valid) -> torch.Tensor:
+    """float64 softmax(q k^T / 8) over the valid pairs, (B, H, Lq, Lk); differentiable in q and k"""
+    s = (_heads(q.double(), H) @ _heads(k.double(), H).transpose(-1, -2)) / math.sqrt(ATTN_HEAD)
+    return torch.softmax(s.masked_fill(~valid.expand(s.shape), float("-inf")), -1)
+
+
+def reference_dropout_attention(q, k, v, do, H: int, valid, keep_mask, p: float):
+    """the truth: float64 autograd of ((softmax(s) * M / (1 - p)) @ V) -> (o, dq, dk, dv)"""
+    q64, k64, v64 = (t.detach().double().clone().requires_grad_(True) for t in (q, k, v))
+    pd = reference_probs(q64, k64, H, valid) * keep_mask.double() / (1.0 - p)
+    o = (pd @ _heads(v64, H)).transpose(1, 2).reshape(q.shape)
+    o.backward(do.double())
+    return o.detach(), q64.grad, k64.grad, v64.grad
+
+
+def _rel_err(got, ref) -> float:
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
+
+
+def check_probe_validity(p64, valid) -> float:
+    """a condition on the reference, not on the kernel: every float64 probability on a valid pair is >= 1e-6, far above where a
+    float32 (or a scaled f16 piece of a) kept probability could vanish, so `Pd > 0` is a faithful mask"""
+    smallest = float(p64[valid.expand(p64.shape)].min())
+    assert smallest >= 1e-6, f"probe validity: smallest reference probability {smallest:.3e} < 1e-6"
+    return smallest
+
+
+def check_same_mask(pd_fwd, pd_bwd, valid) -> torch.Tensor:
+    """the forward's mask is the backward's mask on every valid (b, h, i, j); other pairs give exactly 0 in both probes.
+    Returns the mask (bool, False outside `valid`)."""
+    vm = valid.expand(pd_fwd.shape)
+    for name, pd in (("forward", pd_fwd), ("backward", pd_bwd)):
+        stray = (pd != 0) & ~vm
+        assert not bool(stray.any()), f"same mask: the {name} probe is non-zero on excluded pairs, first at (b, h, i, j) = " \
+                                      f"{tuple(stray.nonzero()[0].tolist())}"
+    mf, mb = (pd_fwd > 0) & vm, (pd_bwd > 0) & vm
+    diff = mf != mb
+    assert not bool(diff.any()), f"same mask: forward and backward differ on {int(diff.sum())} pairs, first at (b, h, i, j) = " \
+                                 f"{tuple(diff.nonzero()[0].tolist())} (forward keeps: {bool(mf[tuple(diff.nonzero()[0].tolist())])})"
+    return mf
+
+
+def check_kept_values(pd_fwd, p64, keep_mask, p: float, rel: float = 2e-5) -> float:
+    """the probed forward matrix is P64 * M / (1 - p) to the attention-output bar (the probe is an attention output)"""
+    err = _rel_err(pd_fwd, p64.detach() * keep_mask.double() / (1.0 - p))
+    assert err <= rel, f"kept values: dropped probabilities are {err:.3e} of their max from P64 * M / (1 - p) (bar {rel:.0e})"
+    return err
+
+
+def check_forward_and_gradients(fwd, bwd, q, k, v, do, H: int, valid, keep_mask, p: float, rel_o: float = 2e-5, rel_g: float = 5e-5):
+    """o, dq, dk, dv with real V and dO against float64 autograd under the probed mask; keys no query may see get exactly zero
+    gradients.  Returns the four relative errors (of the reference's max)."""
+    ro, rq, rk, rv = reference_dropout_attention(q, k, v, do, H, valid, keep_mask, p)
+    o = fwd(q, k, v)
+    dq, dk, dv = bwd(q, k, v, do)
+    errs = dict(o=_rel_err(o, ro), dq=_rel_err(dq, rq), dk=_rel_err(dk, rk), dv=_rel_err(dv, rv))
+    for name, bar in (("o", rel_o), ("dq", rel_g), ("dk", rel_g), ("dv", rel_g)):
+        assert errs[name] <= bar, f"forward and gradients: {name} is {errs[name]:.3e} of its max from fp64 (bar {bar:.0e}); all: {errs}"
+    unseen = ~valid.expand(keep_mask.shape).any(2).any(1)                     # (B, Lk): keys outside every softmax
+    for name, g in (("dk", dk), ("dv", dv)):
+        g = g.detach().cpu()
+        assert float(g[unseen].abs().max() if bool(unseen.any()) else 0.0) == 0.0, f"forward and gradients: {name} of an excluded key is not 0"
+    return errs
+
+
+def check_mask_statistics(keep_mask, kv_len: int, p: float, sigmas: float = 5.0):
+    """keep_mask (B, H, Lq, Lk) bool, keys < kv_len valid.  The keep fraction against the binomial around 1 - floor(p 2^16) / 2^16
+    (the 16-bit threshold, csrc/common.h), and the joint keep frequency of neighbours - columns (2 c, 2 c + 1), which share a hash,
+    columns (2 c + 1, 2 c + 2), rows, heads, samples - against its square: independent decisions.  Pairs are disjoint, so each
+    count is binomial and sigma comes from the element count alone.  Returns {name: (frequency, expectation, n, z)}."""
+    m = keep_mask[..., :kv_len]
+    pk = 1.0 - math.floor(p * 65536.0) / 65536.0
+    out = {}
+
+    def one(name, hits, prob):
+        n = hits.numel()
+        if n == 0:
+            return
+        f = float(hits.double().mean())
+        out[name] = (f, prob, n, (f - prob) / math.sqrt(prob * (1.0 - prob) / n))
+
+    one("keep", m, pk)
+    for dim, what in ((3, "columns"), (2, "rows"), (1, "heads"), (0, "samples")):
+        for off in (0, 1):
+            n = (m.shape[dim] - off) // 2
+            a = m.narrow(dim, off, 2 * n)
+            ix0, ix1 = torch.arange(0, 2 * n, 2), torch.arange(1, 2 * n, 2)
+            one(f"{what} {'2n, 2n+1' if off == 0 else '2n+1, 2n+2'}", a.index_select(dim, ix0) & a.index_select(dim, ix1), pk * pk)
+    for name, (f, prob, n, z) in out.items():
+        assert abs(z) <= sigmas, f"mask statistics: {name}: frequency {f:.5f} over {n} is {z:+.1f} sigma from {prob:.5f}"
+    return out

@@ -977,3 +977,34 @@ def test_residual_dropout_matches_the_add_layernorm_mask(M, D, p):
     y.backward(go)
     assert torch.equal(x.grad, go)
     assert_close(r.grad, torch.where(keep, go / (1.0 - p), torch.zeros_like(go)) if p > 0 else go, rel=2e-6, what="dr")
+
+
+@pytest.mark.parametrize("M,D,p", [(37, 64, 0.3), (1501, 256, 0.1), (130, 512, 0.1)])
+def test_add_layernorm_dropout_backward_matches_fp64(M, D, p):
+    """hoisdf_add_layernorm_fwd / _bwd with dropout on the residual: the mask is read out of hoisdf_residual_dropout(x = NULL,
+    r = ones) at the same seed (include/hoisdf.h: the same (seed, row, column) function), the truth is float64 autograd of
+    LN(x + r * M / (1 - p)): y at the default bar and dx, dr, dgamma, dbeta at 1e-4 as in test_add_layernorm_and_plain; dr is exactly 0
+    where the mask is."""
+    import hoisdf_amd.ops as OO
+    from hoisdf_amd._lib import call
+    seed = (7 << 32) + 5
+    ones = torch.ones(M, D, device=DEV)
+    kept = torch.empty(M, D, device=DEV)
+    call("hoisdf_residual_dropout", None, OO._p(ones), OO._p(kept), M, D, float(p), seed, OO._st())
+    mask = kept.cpu() > 0
+    assert 0.5 * p < 1.0 - float(mask.double().mean()) < 1.5 * p       # a mask, not all or nothing
+    assert_close(kept.cpu()[mask], torch.full((int(mask.sum()),), 1.0 / (1.0 - p)), rel=2e-6, what="kept ones are scaled by 1 / (1 - p)")
+    x, r = rnd(M, D, seed=60).double().requires_grad_(True), rnd(M, D, seed=61).double().requires_grad_(True)
+    g, b = (1 + 0.1 * rnd(D, seed=62)).double().requires_grad_(True), rnd(D, seed=63).double().requires_grad_(True)
+    ref = F.layer_norm(x + r * mask.double() / (1.0 - p), (D,), g, b, 1e-5)
+    gy = rnd(M, D, seed=64)
+    ref.backward(gy.double())
+    xs = [t.detach().float().to(DEV).requires_grad_(True) for t in (x, r, g, b)]
+    y = OO._AddLayerNorm.apply(*xs, 1e-5, p, seed)
+    y.backward(gy.to(DEV))
+    assert_close(y, ref, what="ln with dropout")
+    for a, c, n in zip(xs, (x, r, g, b), ("dx", "dr", "dgamma", "dbeta")):
+        err = float((a.grad.cpu().double() - c.grad).abs().max()) / float(c.grad.abs().max())
+        print(f"add_layernorm dropout ({M}, {D}, p={p}) {n}: {err:.2e} of max")
+        assert_close(a.grad, c.grad, rel=1e-4, what=n)
+    assert float(xs[1].grad.cpu()[~mask].abs().max()) == 0.0
