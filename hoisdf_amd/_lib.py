@@ -121,7 +121,7 @@ class PoseDesc(C.Structure):
                 ("img_w", C.c_int), ("hand_sdf_scale", C.c_float), ("obj_sdf_scale", C.c_float), ("clamping_distance", C.c_float),
                 ("hidden_dim", C.c_int), ("nheads", C.c_int), ("dim_feedforward", C.c_int), ("enc_layers", C.c_int),
                 ("dec_layers", C.c_int), ("C", C.c_int), ("use_inverse_kinematics", C.c_int), ("pre_norm", C.c_int),
-                ("classifier_branch", C.c_int), ("attention", C.c_int)]
+                ("classifier_branch", C.c_int), ("attention", C.c_int), ("ik_solve", C.c_int)]
 
 
 class SdfDecoderParams(C.Structure):
@@ -148,7 +148,7 @@ class EncoderDesc(C.Structure):
 
 
 _POSE_OUT = ("hand_joints_out", "obj_rot_out", "obj_trans_out", "mano_mesh_out", "mano_joints_out", "mano_shape_out",
-             "hand_points_out", "obj_points_out", "hand_sdf_out", "obj_sdf_out")
+             "hand_points_out", "obj_points_out", "hand_sdf_out", "obj_sdf_out", "mano_pose_out", "ik_valid_out")
 
 
 class PoseOutputs(C.Structure):
@@ -233,6 +233,7 @@ SIGNATURES: Dict[str, List] = {
     "hoisdf_mano_prepare": [_P, _P, _P, _P, _P],
     "hoisdf_mano_head_fwd": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     "hoisdf_mano_head_bwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "hoisdf_ik_mano_fwd": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hoisdf_vote_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hoisdf_vote_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hoisdf_vote_loss_fwd": [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],

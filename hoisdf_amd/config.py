@@ -43,6 +43,9 @@ class Config:
     # not in the reference: eval forwards run the stage after the image encoder through ONE C-ABI call (hoisdf_pose_infer) instead of
     # Model.hot_path's Python orchestration; same kernels, no losses in the output (HOISDF_INFER=native does the same)
     native_infer = False
+    # not in the reference: the IK variant's closed-form post-process (hoisdf_amd/ik.py) as one HIP launch (hoisdf_ik_mano_fwd;
+    # with native_infer on, as the last launch of hoisdf_pose_infer).  Also HOISDF_IK=native / test.py --native-ik
+    native_ik = False
     # not in the reference: on that path (eval, no gradient, native_infer on) the image encoder too runs through the C ABI
     # (hoisdf_encoder_infer: BatchNorm folded, exact-f32 HIP convolutions) instead of torch / MIOpen (HOISDF_ENCODER=native does the same)
     native_encoder = False

@@ -14,6 +14,10 @@
 // space is the identity, so the gradient arriving at the layer's rotation is applied to R6 directly - the exact derivative of the
 // same function, without differentiating atan2 / the four-branch quaternion (whose fp32 derivative is noise near the branch
 // edges).  The forward still walks the reference's full conversion chain, so forward values carry the reference's rounding.
+//
+// Inverse kinematics (hoisdf_ik_mano_fwd, the post-process of the IK variant): 21 joints + betas -> the 48 MANO coefficients ->
+// vertices / joints, one launch, one workgroup per hand, around the SAME mano_forward (called at the zero pose for the template
+// and again on the solved pose) - see ik_mano_fwd_kernel below.
 #include "common.h"
 
 namespace hoisdf {
@@ -29,7 +33,7 @@ __constant__ int c_order[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10,
 
 struct ManoArgs {
   const float* pose; int ldpose;      // mode 0: [H][16][6] (ldpose = 96); mode 1: axis-angle coefficients [H][>= 48]
-  const float* betas; int ldbetas;    // [H][>= 10]
+  const float* betas; int ldbetas;    // [H][>= 10]; null = zeros (the IK entry only)
   int mode, H;
   const float* dirs;                  // [145][2334]
   const float* v_template;            // [2334]
@@ -134,7 +138,7 @@ __device__ void mano_forward(const ManoArgs& a, int h, ManoLds& s) {
     }
     rodrigues(full, &s.R[j * 9]);
   }
-  if (tid >= 64 && tid < 64 + MB) s.beta[tid - 64] = a.betas[(size_t)h * a.ldbetas + (tid - 64)];
+  if (tid >= 64 && tid < 64 + MB) s.beta[tid - 64] = a.betas ? a.betas[(size_t)h * a.ldbetas + (tid - 64)] : 0.f;   // null: the mean shape
   __syncthreads();
   if (tid < MPM) s.pm[tid] = s.R[9 + tid] - ((tid % 9) % 4 == 0 ? 1.f : 0.f);
   for (int vc = tid; vc < MVC; vc += MNT) {
@@ -467,6 +471,160 @@ __global__ __launch_bounds__(MNT) void mano_head_bwd_kernel(ManoArgs a) {
   }
 }
 
+// ---- closed-form inverse kinematics of the IK variant (common/utils/inverse_kinematics.py:15-150, main/test.py:139-160), in the
+// arithmetic order of hoisdf_amd/ik.py.  One workgroup per hand, four phases:
+//   1. template: mano_forward at the zero pose (pose_out cleared first and read back as the mode-1 coefficients: Rodrigues of zero is
+//      the identity exactly, the pose blend shapes add exact zeros) -> the 21 template joints, wrist-centred, metres;
+//   2. palm fit: R = V U^T of the SVD of H = T0 P0^T = the orthogonal polar factor of H^T, by Newton's iteration X <- (g X + X^-T / g) / 2
+//      in fp64 on one thread (H sits at 1e-10 .. 1e-7: the matrix is normalised first and every test is relative); a reflection
+//      (det R = -1) leaves the whole pose at zero;
+//   3. fingers: one thread per finger walks its three joints (parent frame and reconstructed chain accumulated), the wrist's
+//      axis-angle is rotation_to_axis_angle of R;
+//   4. posed MANO: mano_forward again on the 48 coefficients just written.
+// The IK state of phases 2-3 (template, target, R) lives in s.vs, which nothing reads between the two forwards: the kernel's LDS is
+// ManoLds, like the head's.  No atomics: two runs give the same bits.
+struct IkArgs {
+  const float* joints; int n_joints;   // 21: [H][21][3], wrist in row 0; 20: [H][20][3] = joints 1..20 relative to a wrist at the origin
+  float* pose;                         // [H][48]; ManoArgs::pose points to the same memory
+  int32_t* valid;                      // [H] or null
+};
+__constant__ int c_palm[5] = {1, 5, 9, 13, 17};
+// joint chains in the 21-joint order; finger g drives MANO pose joints 3 g + 1 .. 3 g + 3   (reference :73-79)
+__constant__ int c_chain[5][5] = {{0, 5, 6, 7, 8}, {0, 9, 10, 11, 12}, {0, 17, 18, 19, 20}, {0, 13, 14, 15, 16}, {0, 1, 2, 3, 4}};
+__constant__ float c_zero_mean[45] = {};
+
+__device__ __forceinline__ double frob3(const double* X) {
+  double t = 0.0;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) t += X[e] * X[e];
+  return sqrt(t);
+}
+// orthogonal polar factor of M (the closest orthogonal matrix; det = sign det M) -> R, returns det R.  A singular M (rank < 3: all-zero
+// joints, exactly coplanar palm bones) has no unique factor: it gives the identity (valid), where torch's SVD returns one particular
+// V U^T - the two paths differ there, on input neither answers meaningfully
+__device__ double polar_orthogonal(const double* M, double* R) {
+  double X[9];
+  const double n0 = frob3(M);
+  bool ok = n0 > 0.0 && n0 < 1e300;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) X[e] = ok ? M[e] / n0 : 0.0;
+  for (int it = 0; ok && it < 60; ++it) {
+    const double C[9] = {X[4] * X[8] - X[5] * X[7], X[5] * X[6] - X[3] * X[8], X[3] * X[7] - X[4] * X[6],
+                         X[2] * X[7] - X[1] * X[8], X[0] * X[8] - X[2] * X[6], X[1] * X[6] - X[0] * X[7],
+                         X[1] * X[5] - X[2] * X[4], X[2] * X[3] - X[0] * X[5], X[0] * X[4] - X[1] * X[3]};   // cofactors: X^-T = C / det
+    const double det = X[0] * C[0] + X[1] * C[1] + X[2] * C[2];
+    const double nx = frob3(X), nc = frob3(C);
+    if (!(fabs(det) > 1e-280 * nx * nx * nx) || !(nc > 0.0)) { ok = false; break; }
+    const double g = sqrt(nc / (fabs(det) * nx));             // |X^-T| / |X|, balanced
+    double diff = 0.0, nn = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+      const double xn = 0.5 * (g * X[e] + C[e] / (det * g));
+      diff += (xn - X[e]) * (xn - X[e]); nn += xn * xn;
+      X[e] = xn;
+    }
+    if (diff <= 1e-24 * nn) break;                             // |X' - X| <= 1e-12 |X'|: quadratic convergence, the next step is exact
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) R[e] = ok ? X[e] : (e % 4 == 0 ? 1.0 : 0.0);
+  return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+}
+
+__global__ __launch_bounds__(MNT) void ik_mano_fwd_kernel(ManoArgs a, IkArgs k) {
+  __shared__ ManoLds s;
+  const int h = blockIdx.x, tid = threadIdx.x;
+  float* pose = k.pose + (size_t)h * 48;
+  a.hands_mean = c_zero_mean;
+  if (tid < 48) pose[tid] = 0.f;
+  __syncthreads();                                           // (the block's own global stores, read back by mano_forward)
+  mano_forward(a, h, s);
+  float* tpl = s.vs; float* tgt = s.vs + 64; float* Rw = s.vs + 128; float* okf = s.vs + 140;
+  const float root[3] = {k.n_joints == 21 ? k.joints[(size_t)h * 63 + 0] : 0.f, k.n_joints == 21 ? k.joints[(size_t)h * 63 + 1] : 0.f,
+                         k.n_joints == 21 ? k.joints[(size_t)h * 63 + 2] : 0.f};
+  if (tid < MJT * 3) {
+    const int i = tid / 3, c = tid - i * 3;
+    tpl[tid] = to_metres(s.cat[c_order[i] * 3 + c] - s.cat[c]);
+    tgt[tid] = k.n_joints == 21 ? k.joints[(size_t)h * 63 + tid] - root[c] : (i == 0 ? 0.f : k.joints[(size_t)h * 60 + tid - 3]);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double M[9], Rd[9];                                        // M = H^T: M[b][a] = sum_k P0[b][k] T0[a][k]
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double acc = 0.0;
+        for (int p = 0; p < 5; ++p) {
+          const int j = c_palm[p];
+          acc += (double)(tgt[j * 3 + b] - tgt[b]) * (double)(tpl[j * 3 + c] - tpl[c]);
+        }
+        M[b * 3 + c] = acc;
+      }
+    const double det = polar_orthogonal(M, Rd);
+    const bool valid = fabs(det + 1.0) > 1e-6;
+    float Rf[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { Rf[e] = (float)Rd[e]; Rw[e] = Rf[e]; }
+    okf[0] = valid ? 1.f : 0.f;
+    if (k.valid) k.valid[h] = valid ? 1 : 0;
+    if (valid) {
+      const float b1[3] = {Rf[0], Rf[3], Rf[6]}, b2[3] = {Rf[1], Rf[4], Rf[7]}, b3[3] = {Rf[2], Rf[5], Rf[8]};   // columns of R = rows of R^T
+      float aa[3];
+      rotation_to_axis_angle(b1, b2, b3, aa);
+      pose[0] = aa[0]; pose[1] = aa[1]; pose[2] = aa[2];
+    }
+  }
+  __syncthreads();
+  if (tid < 5 && okf[0] != 0.f) {
+    const int* ch = c_chain[tid];
+    float Rpa[9], recon[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Rpa[e] = Rw[e];
+    const float lo = (float)(-1.0 + 1e-7), hi = (float)(1.0 - 1e-7);
+    for (int ji = 2; ji < 5; ++ji) {
+      const int j0 = ch[ji - 2] * 3, j1 = ch[ji - 1] * 3, j2 = ch[ji] * 3;
+      const float vt[3] = {tpl[j2] - tpl[j1], tpl[j2 + 1] - tpl[j1 + 1], tpl[j2 + 2] - tpl[j1 + 2]};
+      const float bt[3] = {tpl[j1] - tpl[j0], tpl[j1 + 1] - tpl[j0 + 1], tpl[j1 + 2] - tpl[j0 + 2]};
+      float d[3], vg[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        recon[r] = (Rpa[r * 3] * bt[0] + Rpa[r * 3 + 1] * bt[1] + Rpa[r * 3 + 2] * bt[2]) + recon[r];
+        d[r] = tgt[j2 + r] - recon[r];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) vg[c] = Rpa[c] * d[0] + Rpa[3 + c] * d[1] + Rpa[6 + c] * d[2];
+      float ax[3] = {vt[1] * vg[2] - vt[2] * vg[1], vt[2] * vg[0] - vt[0] * vg[2], vt[0] * vg[1] - vt[1] * vg[0]};
+      const float na = sqrtf(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]) + 1e-7f;
+      const float nt = sqrtf(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]) + 1e-7f;
+      const float ng = sqrtf(vg[0] * vg[0] + vg[1] * vg[1] + vg[2] * vg[2]) + 1e-7f;
+      float cs = (vt[0] * vg[0] + vt[1] * vg[1] + vt[2] * vg[2]) / nt / ng;
+      cs = fminf(fmaxf(cs, lo), hi);
+      const float ang = acosf(cs);
+      const float aa[3] = {ang * (ax[0] / na), ang * (ax[1] / na), ang * (ax[2] / na)};
+      float* o = pose + (tid * 3 + ji - 1) * 3;
+      o[0] = aa[0]; o[1] = aa[1]; o[2] = aa[2];
+      if (ji < 4) {
+        float Rj[9], Rn[9];
+        rodrigues(aa, Rj);                                     // axis_angle_to_matrix of nets/mano.py
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = Rpa[r * 3] * Rj[c] + Rpa[r * 3 + 1] * Rj[3 + c] + Rpa[r * 3 + 2] * Rj[6 + c];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rpa[e] = Rn[e];
+      }
+    }
+  }
+  __syncthreads();                                           // the 48 coefficients are in global memory; s.vs is free again
+  mano_forward(a, h, s);
+  const float cen[3] = {s.cat[0], s.cat[1], s.cat[2]};
+  for (int vc = tid; vc < MVC; vc += MNT) a.verts[(size_t)h * MVC + vc] = to_metres(s.raw[vc] - cen[vc % 3]) + root[vc % 3];
+  if (tid < MJT * 3) {
+    const int i = tid / 3, c = tid - i * 3;
+    a.joints[(size_t)h * MJT * 3 + tid] = to_metres(s.cat[c_order[i] * 3 + c] - cen[c]) + root[c];
+  }
+}
+
 __global__ void mano_transpose_dirs_kernel(const float* __restrict__ shapedirs, const float* __restrict__ posedirs,
                                            const float* __restrict__ weights, float* __restrict__ image) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -537,4 +695,24 @@ extern "C" int hoisdf_mano_head_bwd(const float* pose6d, const float* betas, int
   a.d_pose = d_pose6d; a.d_betas = d_betas;
   hipLaunchKernelGGL(mano_head_bwd_kernel, dim3((unsigned)hands), dim3(MNT), 0, as_stream(stream), a);
   return check_launch("mano_head_bwd");
+}
+
+extern "C" int hoisdf_ik_mano_fwd(const float* joints, int n_joints, const float* betas, int ldbetas, int hands, const float* dirs_image,
+                                  const float* v_template, const float* j_regressor, const float* weights, float* pose_out, float* verts_out,
+                                  float* joints_out, int32_t* valid_out, void* stream) {
+  HOISDF_REQUIRE(hands >= 0 && (n_joints == 20 || n_joints == 21), HOISDF_ERR_INVALID,
+                 "ik_mano_fwd: hands=%d n_joints=%d (21 with the wrist in row 0, or 20 relative to a wrist at the origin)", hands, n_joints);
+  if (hands == 0) return HOISDF_OK;
+  HOISDF_REQUIRE(joints && dirs_image && v_template && j_regressor && weights && pose_out && verts_out && joints_out, HOISDF_ERR_INVALID,
+                 "ik_mano_fwd: null pointer");
+  HOISDF_REQUIRE(!betas || ldbetas >= 10, HOISDF_ERR_INVALID, "ik_mano_fwd: ldbetas=%d", ldbetas);
+  HOISDF_REQUIRE((reinterpret_cast<uintptr_t>(weights) & 15) == 0, HOISDF_ERR_INVALID, "ik_mano_fwd: skinning weights must be 16-byte aligned");
+  ManoArgs a{};
+  a.pose = pose_out; a.ldpose = 48; a.betas = betas; a.ldbetas = ldbetas; a.mode = 1; a.H = hands;
+  a.dirs = dirs_image; a.v_template = v_template; a.j_reg = j_regressor; a.weights = weights;     // hands mean: zero, set by the kernel
+  a.verts = verts_out; a.joints = joints_out;
+  IkArgs k{};
+  k.joints = joints; k.n_joints = n_joints; k.pose = pose_out; k.valid = valid_out;
+  hipLaunchKernelGGL(ik_mano_fwd_kernel, dim3((unsigned)hands), dim3(MNT), 0, as_stream(stream), a, k);
+  return check_launch("ik_mano_fwd");
 }

@@ -263,7 +263,7 @@ __global__ void pose_prep_misc_kernel(const float* __restrict__ hand_beta, const
 }
 
 // ---------------------------------------------------------------- geometry ----------------------------------------------------------------
-struct PGeo { int B, nh, no, S, E, F, H, C, Lh, Lo, Ld, Q; bool ik; long Mh, Mo; };
+struct PGeo { int B, nh, no, S, E, F, H, C, Lh, Lo, Ld, Q; bool ik, iks /* ik_solve */; long Mh, Mo; };
 int pose_geometry(const hoisdf_pose_desc* d, PGeo& g) {
   HOISDF_REQUIRE(d, HOISDF_ERR_INVALID, "pose: null descriptor");
   HOISDF_REQUIRE(d->B > 0 && d->num_samp_hand > 0 && d->num_samp_obj > 0 && d->bins_n > 0 && d->img_h > 0 && d->img_w > 0, HOISDF_ERR_INVALID,
@@ -282,7 +282,9 @@ int pose_geometry(const hoisdf_pose_desc* d, PGeo& g) {
   HOISDF_REQUIRE(!d->pre_norm, HOISDF_ERR_INVALID, "pose: pre_norm is not implemented by the coarse layer entries (post-norm only)");
   HOISDF_REQUIRE(d->attention == 0 || d->attention == 2, HOISDF_ERR_INVALID, "pose: attention must be 0 (exact f32) or 2 (emulated fp32)");
   g.B = d->B; g.nh = d->num_samp_hand; g.no = d->num_samp_obj; g.S = g.nh + g.no; g.E = d->hidden_dim; g.F = d->dim_feedforward; g.H = d->nheads;
+  HOISDF_REQUIRE(!d->ik_solve || d->use_inverse_kinematics, HOISDF_ERR_INVALID, "pose: ik_solve needs use_inverse_kinematics");
   g.C = d->C; g.Lh = d->enc_layers; g.Lo = d->enc_layers / 2; g.Ld = d->dec_layers; g.ik = d->use_inverse_kinematics != 0;
+  g.iks = g.ik && d->ik_solve != 0;
   g.Q = g.ik ? 1 : MANO_Q;
   g.Mh = (long)g.B * g.nh; g.Mo = (long)g.B * g.no;
   HOISDF_REQUIRE((long)g.B * g.S < (1L << 28), HOISDF_ERR_INVALID, "pose: %ld token rows", (long)g.B * g.S);
@@ -448,12 +450,12 @@ int place_all(Placer& P, const PGeo& g, const hoisdf_pose_weights* src, Prep& p)
   p.tgt0 = P.raw((long)g.B * g.Q * E);
   p.mask = static_cast<uint8_t*>(P.b.take((long)g.Q * g.Q));
   p.mano_image = p.mano_tmpl = p.mano_jreg = p.mano_w = p.mano_mean = nullptr;
-  if (!g.ik) {
+  if (!g.ik || g.iks) {                // the MANO head's tables, or the same tables for the IK solve (last in the blob either way)
     p.mano_image = P.raw(hoisdf_mano_dirs_image_floats());
     p.mano_tmpl = P.put(N_VERTS * 3, src ? src->mano_v_template : nullptr, "mano v_template");
     p.mano_jreg = P.put(16 * N_VERTS, src ? src->mano_j_regressor : nullptr, "mano J_regressor");
     p.mano_w = P.put(N_VERTS * 16, src ? src->mano_weights : nullptr, "mano weights");
-    p.mano_mean = P.put(45, src ? src->mano_hands_mean : nullptr, "mano hands_mean");
+    if (!g.ik) p.mano_mean = P.put(45, src ? src->mano_hands_mean : nullptr, "mano hands_mean");   // (the IK solve takes the mean as zero)
   }
   if (!P.copy || P.rc != HOISDF_OK) return P.rc;
   if (!src->hand_sigmoid_beta || !src->obj_sigmoid_beta) { set_error("pose_prepare: null weight sigmoid_beta"); return HOISDF_ERR_INVALID; }
@@ -461,7 +463,7 @@ int place_all(Placer& P, const PGeo& g, const hoisdf_pose_weights* src, Prep& p)
   if (hipMemsetAsync(p.tgt0, 0, sizeof(float) * g.B * g.Q * E, P.st) != hipSuccess) { set_error("pose_prepare: memset failed"); return HOISDF_ERR_LAUNCH; }
   hipLaunchKernelGGL(pose_prep_misc_kernel, dim3(cdiv(g.Q * g.Q, 64)), dim3(64), 0, P.st, src->hand_sigmoid_beta, src->obj_sigmoid_beta, p.betas, p.mask, g.Q);
   if (int rc = check_launch("pose_prepare misc")) return rc;
-  if (!g.ik) {
+  if (!g.ik || g.iks) {
     if (!src->mano_shapedirs || !src->mano_posedirs) { set_error("pose_prepare: null MANO asset"); return HOISDF_ERR_INVALID; }
     if (int rc = hoisdf_mano_prepare(src->mano_shapedirs, src->mano_posedirs, p.mano_w, p.mano_image, P.st)) return rc;
   }
@@ -667,6 +669,8 @@ extern "C" int hoisdf_pose_infer(const hoisdf_pose_desc* desc, const void* prepa
   HOISDF_REQUIRE(out && out->hand_joints_out && out->obj_rot_out && out->obj_trans_out &&
                      (g.ik ? out->mano_shape_out != nullptr : (out->mano_mesh_out && out->mano_joints_out)),
                  HOISDF_ERR_INVALID, "pose_infer: null output (%s)", g.ik ? "hand_joints / obj_rot / obj_trans / mano_shape" : "hand_joints / obj_rot / obj_trans / mano_mesh / mano_joints");
+  HOISDF_REQUIRE(!g.iks || (out->mano_mesh_out && out->mano_joints_out && out->mano_pose_out), HOISDF_ERR_INVALID,
+                 "pose_infer: null output (ik_solve needs mano_mesh_out / mano_joints_out / mano_pose_out)");
   HOISDF_REQUIRE(((reinterpret_cast<uintptr_t>(prepared) | reinterpret_cast<uintptr_t>(workspace)) & 255) == 0, HOISDF_ERR_INVALID,
                  "pose_infer: the prepared blob and the workspace must be 256-byte aligned");
   long pc = 0;
@@ -798,6 +802,10 @@ extern "C" int hoisdf_pose_infer(const hoisdf_pose_desc* desc, const void* prepa
     STEP(vote_only(f.off, f.cls, f.hand_rel, out->hand_joints_out, f.stats, B, nh, J_HAND, sh));
   }
   if (so != sh) STEP(order_after(so, sh, ev[0]));
+  // ---- the IK variant's post-process (main/test.py:139-160): one launch behind the join, on the 20 voted joints and the shape
+  if (g.iks)
+    STEP(hoisdf_ik_mano_fwd(out->hand_joints_out, J_HAND, out->mano_shape_out, N_BETAS, B, p.mano_image, p.mano_tmpl, p.mano_jreg, p.mano_w,
+                            out->mano_pose_out, out->mano_mesh_out, out->mano_joints_out, out->ik_valid_out, vh));
 #undef STEP
   return HOISDF_OK;
 }

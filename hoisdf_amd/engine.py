@@ -282,11 +282,22 @@ class Tester:
     def predict(self, inputs, targets, meta, mano_layer=None):
         """eval forward; for the IK variant (``cfg.use_inverse_kinematics``) the closed-form IK post-process of
         main/test.py:139-160 runs on the device as well when a MANO layer is given: adds ``ik_joints_out`` /
-        ``ik_verts_out`` (root-relative metres, before the caller's mano_root shift) and ``ik_pose_out``."""
+        ``ik_verts_out`` (root-relative metres, before the caller's mano_root shift) and ``ik_pose_out``.  With
+        ``cfg.native_ik`` / ``HOISDF_IK=native`` the post-process is one HIP launch (hoisdf_ik_mano_fwd) - the last launch of
+        hoisdf_pose_infer itself when native inference is on as well."""
+        from .ik import ik_solver_mano, ik_solver_mano_native, native_ik_enabled
         inputs, targets, meta = (T.to_device(x, self.device) for x in (inputs, targets, meta))
+        ik = self.cfg.use_inverse_kinematics and mano_layer is not None
+        native = ik and native_ik_enabled(self.cfg)
+        if native and self.model.ik_mano_layer is not mano_layer:
+            self.model.set_ik_mano_layer(mano_layer)             # (moved to the device by the first native call that reads it)
         out = self.model(inputs, targets, meta, "eval")
-        if self.cfg.use_inverse_kinematics and mano_layer is not None:
-            from .ik import ik_solver_mano
+        if native and "ik_pose_out" not in out:          # (there already: hoisdf_pose_infer ran the solve)
+            if next(mano_layer.buffers()).device != out["hand_joints_out"].device:
+                mano_layer.to(self.device)
+            r = ik_solver_mano_native(mano_layer, out.get("mano_shape_out"), out["hand_joints_out"])
+            out["ik_joints_out"], out["ik_verts_out"], out["ik_pose_out"] = r["joints"], r["verts"], r["pose"]
+        elif ik and not native:
             hj = torch.cat([torch.zeros_like(out["hand_joints_out"][:, :1]), out["hand_joints_out"]], 1)
             r = ik_solver_mano(mano_layer.to(self.device), out.get("mano_shape_out"), hj)
             out["ik_joints_out"], out["ik_verts_out"], out["ik_pose_out"] = r["joints"], r["verts"], r["pose"]

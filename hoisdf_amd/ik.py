@@ -10,9 +10,14 @@ kornia (``rotation_matrix_to_axis_angle``, :9 / :70) is supplied to it as a rest
 (four-branch matrix -> quaternion with the 1e-8 guard, then 2 atan2 / sin: tests/golden/make_golden.py ik_golden) instead of
 round 5's scipy log map, so the fixture carries the reference's arithmetic; poses (as vectors and as rotations), joints and
 vertices agree to 2e-5 (tests/test_ik.py, CPU and on the device), next to the property the algorithm guarantees (MANO(pose from
-IK) reproduces the target joints)."""
+IK) reproduces the target joints).
+
+``ik_solver_mano_native`` is the same post-process as ONE HIP launch (csrc/mano.hip ik_mano_fwd_kernel through
+ops.ik_mano / hoisdf_ik_mano_fwd), opt-in (``cfg.native_ik`` / ``HOISDF_IK=native``), held to the same fixture at the same bars
+(tests/test_gpu_ik_native.py); ``ik_solver_mano`` stays the yardstick."""
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -66,3 +71,24 @@ def ik_solver_mano(mano_layer: ManoLayer, mano_shape: Optional[torch.Tensor], pr
     verts, joints = mano_layer(pose_aa.reshape(B, -1), shape)
     return {"verts": verts / 1000.0 + root, "joints": joints / 1000.0 + root, "shape": shape,
             "pose": pose_aa.reshape(B, -1), "vis": valid[:, None].long()}
+
+
+def native_ik_enabled(cfg=None) -> bool:
+    """cfg.native_ik (default False) or HOISDF_IK=native: the IK post-process runs as one HIP launch (ik_solver_mano_native)"""
+    return bool(getattr(cfg, "native_ik", False)) or os.environ.get("HOISDF_IK", "") == "native"
+
+
+@torch.no_grad()
+def ik_solver_mano_native(mano_layer: ManoLayer, mano_shape: Optional[torch.Tensor], pred_joints: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``ik_solver_mano`` through hoisdf_ik_mano_fwd: same arguments, same dict.  GPU only, and only for the layer the kernels hold
+    (centred on the wrist, zero hand mean): anything else is an error, not a fall-back to the torch solver."""
+    from . import ops
+    assets = mano_layer.kernel_assets()
+    if assets is None:
+        raise RuntimeError("ik_solver_mano_native needs this package's ManoLayer on the GPU, centred on the wrist, with a zero hand mean "
+                           "(the configuration of the reference, main/model.py:735-742)")
+    B = pred_joints.shape[0]
+    shape = None if mano_shape is None else mano_shape.detach().float()
+    pose, verts, joints, valid = ops.ik_mano(pred_joints[:, :21].float(), shape, assets)
+    return {"verts": verts, "joints": joints, "shape": torch.zeros(B, 10, device=pred_joints.device) if shape is None else shape,
+            "pose": pose, "vis": valid[:, None].long()}

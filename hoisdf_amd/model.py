@@ -159,6 +159,19 @@ class Model(nn.Module):
         self._py_random = random            # the p < 0.4 branch draw (reference :426); injectable for tests
         self._jitter = None                 # test hook: callable(like, d) -> jitter tensor
         self._side_stream = None            # the second HIP stream, made by the first two-stream _stream_plan
+        # the IK variant owns no MANO layer (its state_dict has no mano_head.*): the layer its native post-process solves with is a
+        # plain attribute, NOT a registered submodule (the checkpoint schema stays as it is)
+        self.set_ik_mano_layer(mano_layer if cfg.use_inverse_kinematics else None)
+
+    def set_ik_mano_layer(self, mano_layer):
+        object.__setattr__(self, "ik_mano_layer", mano_layer)
+
+    def _ik_layer(self, device):
+        """the IK solve's layer on ``device``: as no submodule it does not follow Model.to, so the first native call moves it (once)"""
+        ml = self.ik_mano_layer
+        if ml.th_shapedirs.device != torch.device(device):
+            ml.to(device)
+        return ml
 
     def freeze_stages(self):
         if self.backbone_net is None:
@@ -483,6 +496,12 @@ class Model(nn.Module):
         """cfg.native_infer (default False) or HOISDF_INFER=native: Model.forward in eval mode runs infer_native instead of hot_path"""
         return bool(getattr(self.cfg, "native_infer", False)) or os.environ.get("HOISDF_INFER", "") == "native"
 
+    def native_ik_enabled(self) -> bool:
+        """cfg.native_ik (default False) or HOISDF_IK=native, for the IK variant with a MANO layer to solve with: infer_native asks
+        hoisdf_pose_infer for the closed-form IK post-process too (ik_solve = 1) -> ik_joints_out / ik_verts_out / ik_pose_out"""
+        from .ik import native_ik_enabled
+        return bool(self.cfg.use_inverse_kinematics) and self.ik_mano_layer is not None and native_ik_enabled(self.cfg)
+
     def _pose_desc(self, B, C_):
         from ._lib import PoseDesc
         c = self.cfg
@@ -490,7 +509,8 @@ class Model(nn.Module):
                         img_w=c.input_img_shape[1], hand_sdf_scale=c.hand_sdf_scale, obj_sdf_scale=c.obj_sdf_scale,
                         clamping_distance=c.ClampingDistance, hidden_dim=c.hidden_dim, nheads=c.nheads, dim_feedforward=c.dim_feedforward,
                         enc_layers=c.enc_layers, dec_layers=c.dec_layers, C=C_, use_inverse_kinematics=int(c.use_inverse_kinematics),
-                        pre_norm=int(c.pre_norm), classifier_branch=int(c.ClassifierBranch), attention=2 if ops.attention_emu() else 0)
+                        pre_norm=int(c.pre_norm), classifier_branch=int(c.ClassifierBranch), attention=2 if ops.attention_emu() else 0,
+                        ik_solve=int(self.native_ik_enabled()))
 
     def _pose_weights(self):
         """hoisdf_pose_weights from the module's own parameters -> (struct, the tensors it points to)"""
@@ -546,9 +566,13 @@ class Model(nn.Module):
         mlp(w.linear_handcls, self.linear_handcls, False)
         mlp(w.linear_obj_rot, self.linear_obj_rot, False)
         mlp(w.linear_obj_rel_trans, self.linear_obj_rel_trans, False)
-        if not self.cfg.use_inverse_kinematics:
-            mlp(w.linear_pose, self.linear_pose, False)
-            ml = self.mano_head.mano_layer
+        iks = self.native_ik_enabled()
+        if not self.cfg.use_inverse_kinematics or iks:
+            if iks:
+                ml = self._ik_layer(self.hand_sigmoid_beta.device)
+            else:
+                mlp(w.linear_pose, self.linear_pose, False)
+                ml = self.mano_head.mano_layer
             if ml.kernel_assets() is None:
                 raise RuntimeError("infer_native needs this package's ManoLayer on the GPU, centred on the wrist, with a zero hand mean "
                                    "(the configuration of the reference, main/model.py:735-742)")
@@ -561,7 +585,10 @@ class Model(nn.Module):
         when a parameter, the batch size or an arithmetic switch changed - the key of the SDF-query folds, over every parameter"""
         ps = [p for n, p in self.named_parameters() if not n.startswith(("backbone_net", "decoder_net"))] + \
              [b for n, b in self.named_buffers() if n.startswith("mano_head")]
-        key = (B, C_, str(device), ops._WEIGHT_GEN[0], ops.gemm_emu(), ops.attention_emu()) + tuple((p.data_ptr(), p._version) for p in ps)
+        iks = self.native_ik_enabled()
+        if iks:                         # the layer the IK solve reads is no submodule: its asset tensors join the key by hand
+            ps += [b for n, b in self._ik_layer(device).named_buffers() if n.startswith("th_")]
+        key = (B, C_, str(device), ops._WEIGHT_GEN[0], ops.gemm_emu(), ops.attention_emu(), iks) + tuple((p.data_ptr(), p._version) for p in ps)
         ent = _POSE_CACHE.get(self)
         if ent is None:
             ent = _POSE_CACHE[self] = {"key": None, "prepared": None, "builds": 0}
@@ -576,7 +603,8 @@ class Model(nn.Module):
     @torch.no_grad()
     def infer_native(self, pyr, meta_info, counts=None, debug=False) -> Dict[str, torch.Tensor]:
         """The eval forward of hot_path through ONE C-ABI call (hoisdf_pose_infer): pyramid + camera inputs + boxes ->
-        hand_joints_out, obj_rot_out, obj_trans_out and mano_mesh_out + mano_joints_out (or mano_shape_out for the IK variant),
+        hand_joints_out, obj_rot_out, obj_trans_out and mano_mesh_out + mano_joints_out (or mano_shape_out for the IK variant; with
+        native_ik_enabled() also that variant's post-process: ik_joints_out / ik_verts_out / ik_pose_out / ik_valid_out),
         same keys and shapes as hot_path(..., "eval")'s outputs.  No losses, no ground-truth MANO outputs.  ``counts``: what
         infer_native_begin queued ahead of the encoder.  The default arithmetic only (cfg.attention_f16_eval is not offered)."""
         pyr = self._pyramid(pyr)

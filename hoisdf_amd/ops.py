@@ -1954,6 +1954,35 @@ def mano_gt(mano_param, assets):
     return verts, joints, rot
 
 
+@torch.no_grad()
+def ik_mano(joints, betas, assets):
+    """(f3) the closed-form inverse kinematics of the IK variant + the MANO layer on its result in ONE launch (hoisdf_ik_mano_fwd):
+    joints (H,21,3) metres with the wrist in row 0, or (H,20,3) = joints 1..20 relative to a wrist at the origin; betas (H, >= 10)
+    with unit inner stride (any row stride) or None = zeros; assets as mano_head takes them (hands_mean must be zero) ->
+    pose (H,48) axis-angle, verts (H,778,3) and joints (H,21,3) in metres at the input wrist, valid (H,) int32 = 0 where the palm
+    fit is a reflection (that hand keeps the zero pose)."""
+    joints = joints.contiguous().float()
+    H, nj = joints.shape[0], joints.shape[1]
+    assert joints.dim() == 3 and nj in (20, 21) and joints.shape[2] == 3, tuple(joints.shape)
+    ld = 0
+    if betas is not None:
+        betas = betas.float()
+        assert betas.dim() == 2 and betas.shape[0] == H and betas.shape[1] >= 10, tuple(betas.shape)
+        if betas.stride(1) != 1 or betas.stride(0) < 10:
+            betas = betas[:, :10].contiguous()
+        ld = betas.stride(0)
+    _chk(joints, betas)
+    dev = joints.device
+    pose = torch.empty(H, 48, device=dev, dtype=torch.float32)
+    verts = torch.empty(H, 778, 3, device=dev, dtype=torch.float32)
+    out_joints = torch.empty(H, 21, 3, device=dev, dtype=torch.float32)
+    valid = torch.empty(H, device=dev, dtype=torch.int32)
+    image, tmpl, jreg, w = assets[:4]
+    call("hoisdf_ik_mano_fwd", _p(joints), nj, _p(betas), ld, H, _p(image), _p(tmpl), _p(jreg), _p(w), _p(pose), _p(verts), _p(out_joints),
+         _p(valid), _st())
+    return pose, verts, out_joints, valid
+
+
 # ---------------------------------------------------------------------------------------------
 # (f4) auxiliary image losses of the encoder outputs
 # ---------------------------------------------------------------------------------------------
@@ -2126,7 +2155,8 @@ class PoseInferCounts:
 def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr, bbox_hand, bbox_obj, counts: Optional[PoseInferCounts] = None,
                side_stream=None, debug: bool = False):
     """hoisdf_pose_infer: the eval forward of everything after the image encoder in ONE C-ABI call -> dict of the ``*_out`` tensors
-    (with ``debug`` also the selected points and their SDF values).  Raises ValueError when a sample has fewer lattice survivors
+    (with ``debug`` also the selected points and their SDF values; with the descriptor's ``ik_solve`` also ``ik_joints_out`` /
+    ``ik_verts_out`` / ``ik_pose_out`` / ``ik_valid_out``, root-relative).  Raises ValueError when a sample has fewer lattice survivors
     than requested points (nothing is launched then)."""
     d = prepared.desc
     dev = root.device
@@ -2136,8 +2166,13 @@ def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr,
     B, nh, no = d.B, d.num_samp_hand, d.num_samp_obj
     e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
     out = {"hand_joints_out": e(B, 20, 3), "obj_rot_out": e(B, no, 3), "obj_trans_out": e(B, no, 3)}
+    c_names = {}                 # this dict's key -> the field of hoisdf_pose_outputs, where they differ
     if d.use_inverse_kinematics:
         out["mano_shape_out"] = e(B, 10)
+        if d.ik_solve:           # the IK post-process as the call's last launch, under the keys engine.Tester.predict uses
+            out.update(ik_joints_out=e(B, 21, 3), ik_verts_out=e(B, 778, 3), ik_pose_out=e(B, 48),
+                       ik_valid_out=torch.empty(B, device=dev, dtype=torch.int32))
+            c_names = {"ik_joints_out": "mano_joints_out", "ik_verts_out": "mano_mesh_out", "ik_pose_out": "mano_pose_out"}
     else:
         out["mano_mesh_out"], out["mano_joints_out"] = e(B, 778, 3), e(B, 21, 3)
     if debug:
@@ -2153,7 +2188,7 @@ def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr,
     if nbytes < 0:
         raise ValueError(lib().hoisdf_last_error().decode())
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    o = PoseOutputs(**{k: v.data_ptr() for k, v in out.items()})
+    o = PoseOutputs(**{c_names.get(k, k): v.data_ptr() for k, v in out.items()})
     cur = torch.cuda.current_stream(dev)
     if prepared.stream != cur:
         cur.wait_event(prepared.event)

@@ -718,7 +718,16 @@ int hoisdf_point_loss_bwd(const float* pred, const float* target, long n, long r
  * hoisdf_mano_head_bwd (mode 0 inputs again; nothing is saved between the calls): upstream gradients g_loss_sums
  *   [hands][4], g_verts, g_joints, g_rot (each may be NULL = zero) -> d_pose6d [hands][16][6], d_betas [hands][10].
  *   hands_mean must be zero (flat_hand_mean=True): the backward applies the layer's rotation gradient to the 6D rotation
- *   directly, which is exact only then (csrc/mano.hip header). */
+ *   directly, which is exact only then (csrc/mano.hip header).
+ * hoisdf_ik_mano_fwd: the closed-form inverse kinematics of the IK variant (common/utils/inverse_kinematics.py:15-150 as
+ *   main/test.py:139-160 applies it) and the MANO layer on its result, ONE launch for `hands` hands (hands mean zero):
+ *   joints with n_joints = 21: [hands][21][3] metres, wrist in row 0 at any translation; n_joints = 20: [hands][20][3] = joints
+ *   1..20 relative to a wrist at the origin (the layout of hoisdf_pose_outputs.hand_joints_out); betas [hands][>= 10] with row
+ *   stride ldbetas, NULL = zeros.  The palm fit (Kabsch over the five palm bones) is a proper rotation or a reflection:
+ *   valid_out [hands] (may be NULL) = 1 / 0, and a reflected hand keeps the zero pose.  A SINGULAR fit (all-zero joints, exactly
+ *   coplanar palm bones: rank < 3) takes the identity as the palm rotation with valid = 1, where an SVD would return one of the
+ *   equally good rotations - degenerate input, not a case either solver answers meaningfully.  pose_out [hands][48] axis-angle,
+ *   verts_out [hands][778][3] and joints_out [hands][21][3] in metres at the input wrist.  No atomics: two calls, same bits. */
 long hoisdf_mano_dirs_image_floats(void);
 int hoisdf_mano_prepare(const float* shapedirs, const float* posedirs, const float* weights, float* image, void* stream);
 int hoisdf_mano_head_fwd(const float* pose, int ldpose, int mode, const float* betas, int ldbetas, int hands,
@@ -731,6 +740,9 @@ int hoisdf_mano_head_bwd(const float* pose6d, const float* betas, int hands, con
                          const float* gt_joints, const float* gt_rot, const float* gt_shape, int ldgt_shape, int gt_hands,
                          const float* g_loss_sums, const float* g_verts, const float* g_joints, const float* g_rot,
                          float* d_pose6d, float* d_betas, void* stream);
+int hoisdf_ik_mano_fwd(const float* joints, int n_joints, const float* betas, int ldbetas, int hands,
+                       const float* dirs_image, const float* v_template, const float* j_regressor, const float* weights,
+                       float* pose_out, float* verts_out, float* joints_out, int32_t* valid_out, void* stream);
 
 /* ---- whole-model inference: the stage after the image encoder as ONE entry ---------------------------------------------
  * reference: the eval forward of Model.forward behind decoder_net (main/model.py:424-662, the sdf_infer branch :462-481): feature
@@ -763,6 +775,8 @@ typedef struct hoisdf_pose_desc {
   int pre_norm;                    /* cfg.pre_norm: refused (the coarse layer entries are post-norm) */
   int classifier_branch;           /* cfg.ClassifierBranch: the class logits are read by nothing in this path; accepted, no effect */
   int attention;                   /* 0: exact-f32 attention kernels; 2: emulated fp32 (the default of hoisdf_encoder_layer_desc) */
+  int ik_solve;                    /* with use_inverse_kinematics only: 1 = hoisdf_ik_mano_fwd on hand_joints_out + mano_shape_out as the
+                                      call's last launch -> mano_pose_out, mano_mesh_out, mano_joints_out (the MANO assets become required) */
 } hoisdf_pose_desc;
 #define HOISDF_POSE_MAX_LAYERS 12
 /* hand_sdf_decoder.* / obj_sdf_decoder.* as checkpointed (torch weight_norm, legacy naming) */
@@ -789,19 +803,24 @@ typedef struct hoisdf_pose_weights {
   hoisdf_mlp linear_handcls;               /* hidden -> hidden -> hidden -> 20 */
   hoisdf_mlp linear_obj_rot;               /* hidden -> hidden -> hidden -> 3 */
   hoisdf_mlp linear_obj_rel_trans;         /* hidden -> hidden -> hidden -> 3 */
-  /* MANO assets (unused with use_inverse_kinematics): what hoisdf_mano_prepare / hoisdf_mano_head_fwd take; hands_mean must be zero */
+  /* MANO assets (unused with use_inverse_kinematics unless ik_solve): what hoisdf_mano_prepare / hoisdf_mano_head_fwd take; hands_mean must be
+   * zero.  With ik_solve mano_hands_mean is NOT read (may be NULL): hoisdf_ik_mano_fwd solves for a layer with a zero hand mean
+   * (flat_hand_mean=True), and a host whose layer has another mean must not use it */
   const float *mano_shapedirs, *mano_posedirs, *mano_weights, *mano_v_template, *mano_j_regressor, *mano_hands_mean;
 } hoisdf_pose_weights;
 typedef struct hoisdf_pose_outputs {
   float* hand_joints_out;          /* [B][20][3] */
   float* obj_rot_out;              /* [B][num_samp_obj][3] */
   float* obj_trans_out;            /* [B][num_samp_obj][3] */
-  float* mano_mesh_out;            /* [B][778][3]  (not with use_inverse_kinematics) */
-  float* mano_joints_out;          /* [B][21][3]   (not with use_inverse_kinematics) */
+  float* mano_mesh_out;            /* [B][778][3]  (with use_inverse_kinematics: only with ik_solve, the IK result, wrist at the origin) */
+  float* mano_joints_out;          /* [B][21][3]   (the same) */
   float* mano_shape_out;           /* [B][10]      (use_inverse_kinematics only) */
   /* optional debug outputs (NULL = skipped): the selected points (scaled SDF frame) and their clamped SDF values */
   float *hand_points_out, *obj_points_out;   /* [B][num_samp_*][3] */
   float *hand_sdf_out, *obj_sdf_out;         /* [B][num_samp_*] */
+  /* ik_solve only */
+  float* mano_pose_out;            /* [B][48] axis-angle MANO coefficients */
+  int32_t* ik_valid_out;           /* [B], optional: 1 = the palm fit is a proper rotation, 0 = a reflection (pose left at zero) */
 } hoisdf_pose_outputs;
 long hoisdf_pose_prepared_bytes(const hoisdf_pose_desc* desc);
 int hoisdf_pose_prepare(const hoisdf_pose_desc* desc, const hoisdf_pose_weights* weights, void* prepared, long prepared_bytes,

@@ -34,6 +34,8 @@ def parse_args():
                     help="run everything after the image encoder through the one C entry hoisdf_pose_infer (cfg.native_infer)")
     ap.add_argument("--native-encoder", action="store_true",
                     help="with --native-infer: the image encoder too through the C ABI (hoisdf_encoder_infer, cfg.native_encoder)")
+    ap.add_argument("--native-ik", action="store_true",
+                    help="the IK variant's closed-form post-process as one HIP launch (hoisdf_ik_mano_fwd, cfg.native_ik)")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -47,6 +49,7 @@ def main():
     cfg.apply_setting(a.setting)
     cfg.native_infer = bool(a.native_infer)
     cfg.native_encoder = bool(a.native_encoder)
+    cfg.native_ik = bool(a.native_ik)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
