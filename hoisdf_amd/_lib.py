@@ -255,6 +255,12 @@ SIGNATURES: Dict[str, List] = {
     "hoisdf_encoder_prepare": [_P, _P, _I, _P, _L, _P],
     "hoisdf_encoder_pyramid_shape": [_P, _PYR],
     "hoisdf_encoder_infer": [_P, _P, _P, _P, _P, _P, _L, _P],
+    "hoisdf_eval_object": [_P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "hoisdf_eval_hand_joints": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "hoisdf_eval_mesh": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "hoisdf_eval_accum_init": [_P, _I, _I, _P],
+    "hoisdf_eval_accum_feed": [_P, _P, _I, _I, _P, _I, _P],
+    "hoisdf_eval_accum_finish": [_P, _I, _P, _I, _P, _P],
 }
 _RET = {"hoisdf_version": C.c_char_p, "hoisdf_last_error": C.c_char_p}
 _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I], None), "hoisdf_get_gemm_emu": ([], C.c_int), "hoisdf_get_deterministic": ([], C.c_int),
@@ -296,6 +302,8 @@ _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I]
           "hoisdf_encoder_prepared_bytes": ([_P], C.c_long),
           "hoisdf_encoder_infer_workspace": ([_P], C.c_long),
           "hoisdf_encoder_launch_count": ([_P], C.c_int),
+          "hoisdf_eval_workspace_bytes": ([_I, _I], C.c_long),
+          "hoisdf_eval_accum_state_bytes": ([_I, _I], C.c_long),
           "hoisdf_pose_prepared_bytes": ([_P], C.c_long),
           "hoisdf_pose_infer_workspace": ([_P, _P], C.c_long)}
 

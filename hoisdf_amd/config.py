@@ -46,6 +46,10 @@ class Config:
     # not in the reference: the IK variant's closed-form post-process (hoisdf_amd/ik.py) as one HIP launch (hoisdf_ik_mano_fwd;
     # with native_infer on, as the last launch of hoisdf_pose_infer).  Also HOISDF_IK=native / test.py --native-ik
     native_ik = False
+    # not in the reference: the evaluation metrics of test.py (hoisdf_amd/metrics.py Evaluator) through the hoisdf_eval_* entries
+    # (csrc/eval.hip) instead of batched torch; the running sums stay on the device until results.txt is written.  Also
+    # HOISDF_METRICS=native / test.py --native-metrics
+    native_metrics = False
     # not in the reference: on that path (eval, no gradient, native_infer on) the image encoder too runs through the C ABI
     # (hoisdf_encoder_infer: BatchNorm folded, exact-f32 HIP convolutions) instead of torch / MIOpen (HOISDF_ENCODER=native does the same)
     native_encoder = False

@@ -10,10 +10,16 @@
 The reference loops over samples on the host (numpy SVD per sample, open3d nearest neighbours per mesh); here every
 metric is one batched torch expression on the GPU (the N x N distance matrices of ADD-S / F-score are 778^2 ... 2000^2
 per sample).  Object templates are dataset assets (YCB models) - callers pass ``templates[obj_id] = (V, 3)`` tensors.
+
+The ``*_native`` functions and ``MeshEvalNative`` are the same metrics through the hoisdf_eval_* entries of the C ABI (csrc/eval.hip,
+ops.eval_*): no distance matrix, an fp64 Jacobi SVD in the kernel, integer threshold counts, running mesh sums on the device.
+Opt-in (``cfg.native_metrics`` / ``HOISDF_METRICS=native`` / ``test.py --native-metrics``); GPU only, no fallback.  ``Evaluator`` is
+the per-batch bookkeeping of test.py over either backend.
 """
 from __future__ import annotations
 
 import json
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -151,3 +157,200 @@ def dump_pred_mano(path: str, xyz_pred_list, verts_pred_list) -> None:
     """pred_mano.json of the HO3D submission format (data/ho3d_util.py:123-134): [[joints...], [verts...]]."""
     with open(path, "w") as fo:
         json.dump([[np.asarray(x).tolist() for x in xyz_pred_list], [np.asarray(v).tolist() for v in verts_pred_list]], fo)
+
+
+# ---- the same metrics through the C ABI (csrc/eval.hip) ----------------------------------------------------------------
+def native_metrics_enabled(cfg=None) -> bool:
+    """cfg.native_metrics (default False) or HOISDF_METRICS=native: the Evaluator runs the hoisdf_eval_* entries"""
+    return bool(getattr(cfg, "native_metrics", False)) or os.environ.get("HOISDF_METRICS", "") == "native"
+
+
+def obj_metrics_native(obj_rot, obj_trans, obj_rot_gt, obj_trans_gt, templates, obj_ids, ho3d: bool):
+    """``obj_metrics`` through hoisdf_eval_object.  The template of each sample is named, not gathered: templates (T,V,3) and
+    obj_ids (B,) (``obj_metrics`` takes templates[obj_ids]).  Same dict of per-batch means (one read-back)."""
+    from . import ops
+    adds, mce, oce, mme, _ = ops.eval_object(obj_rot, obj_trans, obj_rot_gt, obj_trans_gt, templates, obj_ids)
+    m = torch.stack([adds.mean(), mce.mean(), oce.mean(), mme.mean()]).tolist()
+    return {"ADDS": m[0], "MME": m[3]} if ho3d else {"ADDS": m[0], "MCE": m[1], "OCE": m[2]}
+
+
+def rigid_align_native(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """``rigid_align`` through hoisdf_eval_hand_joints (any number of points)"""
+    from . import ops
+    return ops.eval_hand_joints(A, B, want_aligned=True)[2]
+
+
+def eval_hand_joint_native(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[float, float]:
+    """``eval_hand_joint`` through hoisdf_eval_hand_joints: (MJE, PA-MJE) batch means (one read-back)"""
+    from . import ops
+    mje, pa = ops.eval_hand_joints(pred, gt)[:2]
+    m = torch.stack([mje.mean(), pa.mean()]).tolist()
+    return m[0], m[1]
+
+
+def fscore_native(gt: torch.Tensor, pr: torch.Tensor, th: float) -> torch.Tensor:
+    """``fscore`` through hoisdf_eval_mesh: per-sample F-score of pr against gt at threshold th, no alignment.  (The Evaluator
+    asks for every threshold, raw and aligned, in one call: ops.eval_mesh.)"""
+    from . import ops
+    return ops.eval_mesh(pr, gt, [float(th)])[2][:, 0]
+
+
+class MeshEvalNative:
+    """``MeshEval`` on the device (hoisdf_eval_accum_*): one fp64 sum per vertex and one count per (threshold, vertex) instead of
+    every distance of the test set on the host.  The thresholds are fixed when the object is made, since the counts are taken as
+    the samples arrive; ``get_measures`` must be asked for the same ones.  The MEDIAN error needs every distance and is not
+    provided: ``get_measures`` returns NaN in its place (results.txt does not print it)."""
+
+    def __init__(self, val_min: float = 0.0, val_max: float = 0.05, steps: int = 100):
+        self.range = (float(val_min), float(val_max), int(steps))
+        self.th = np.linspace(val_min, val_max, steps)
+        self.state = self.th_dev = None
+        self.V = 0
+
+    def feed_dist(self, dist: torch.Tensor):
+        """per-vertex distances (B,V) float32 on the device, as ops.eval_mesh returns them"""
+        from . import ops
+        if self.state is None:
+            self.V = dist.shape[1]
+            self.th_dev = ops.eval_thresholds(self.th, dist.device)
+            self.state = ops.eval_accum_init(self.V, len(self.th), dist.device)
+        assert dist.shape[1] == self.V, (tuple(dist.shape), self.V)
+        ops.eval_accumulate(self.state, dist, self.th_dev)
+
+    def feed(self, gt: torch.Tensor, pred: torch.Tensor):
+        from . import ops
+        self.feed_dist(ops.eval_hand_joints(pred, gt, want_dist=True)[4])
+
+    def measures_device(self) -> torch.Tensor:
+        """(2 + steps,) float64 on the device: mean EPE, AUC, PCK curve; nothing is read back"""
+        from . import ops
+        assert self.state is not None, "MeshEvalNative: nothing was fed"
+        return ops.eval_accum_finish(self.state, self.V, self.th_dev)
+
+    def get_measures(self, val_min: float, val_max: float, steps: int):
+        assert (float(val_min), float(val_max), int(steps)) == self.range, ((val_min, val_max, steps), self.range)
+        m = self.measures_device().cpu().numpy()
+        return float(m[0]), float("nan"), float(m[1]), m[2:].copy(), self.th
+
+
+# ---- the per-batch bookkeeping of the test driver (main/test.py:100-265) -----------------------------------------------
+# data/ho3d.py:47-70: jointsMapSimpleToMano = argsort(jointsMapManoToSimple) - the order of the HO3D submission file
+JOINTS_SIMPLE_TO_MANO = [0, 5, 6, 7, 9, 10, 11, 17, 18, 19, 13, 14, 15, 1, 2, 3, 4, 8, 12, 16, 20]
+F_THRESHS = [0.005, 0.015]
+
+
+class Evaluator:
+    """Running evaluation of a test set: ``feed`` one batch of model outputs, ``write`` results.txt (and pred_mano.json for ho3d).
+    templates (T,V,3) on the evaluation device; obj_cls (B,) = the template of each sample.  ``native=False`` is the batched torch
+    path (every ``feed`` reads its batch means back); ``native=True`` runs the hoisdf_eval_* entries, keeps the running sums, the
+    F-scores and the mesh accumulators on the device and reads them once in ``write``.  Only the native path knows samples that are not
+    evaluated (obj_cls < 0): they count for the hand keys and not for the object keys (*_error)."""
+
+    def __init__(self, cfg, templates: torch.Tensor, native: bool = False):
+        self.cfg, self.templates, self.native = cfg, templates, bool(native)
+        self.dev = templates.device
+        self.ho3d = cfg.dataset == "ho3d"
+        keys = ["ADDS_error"] + (["MME_error"] if self.ho3d else ["mano_mje", "mano_pamje", "OCE_error", "MCE_error"])
+        self.results = {k: 0.0 for k in keys}                 # torch path: running sums on the host, in cm
+        # native path: one device vector - the sum of every key's per-sample values [m], then the number of samples whose object was
+        # evaluated (hoisdf_eval_object's used flag); one stacked reduction per batch, read once in write()
+        self._acc = torch.zeros(len(keys) + 1, device=self.dev, dtype=torch.float64) if self.native else None
+        self.total = 0
+        if self.ho3d:
+            self.coord_change = torch.tensor([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]], device=self.dev)
+            self.joint_list, self.mesh_list = [], []
+        else:
+            cls = MeshEvalNative if self.native else MeshEval
+            self.mesh_err, self.mesh_err_al = cls(), cls()
+            self.f_score, self.f_score_al, self.f_threshs = [], [], list(F_THRESHS)
+            self._fth = None
+
+    def _add(self, vals, B, used=None):
+        """vals: key -> the batch mean on the host (torch path) or the per-sample device values (native path)"""
+        if self.native:
+            self._acc += torch.stack([vals[k] for k in self.results] + [used.float()]).sum(1, dtype=torch.float64)
+        else:
+            for k, v in vals.items():
+                self.results[k] += v * B * 100
+
+    def feed(self, out, targets, meta, obj_cls) -> None:
+        from . import ops
+        cfg, dev, ho3d = self.cfg, self.dev, self.ho3d
+        B = meta["mano_root"].shape[0]
+        tg = {k: v.to(dev) for k, v in targets.items()}
+        root = meta["mano_root"].to(dev)
+        if self.native:
+            adds, mce, oce, mme, used = ops.eval_object(out["obj_rot_out"], out["obj_trans_out"], tg["obj_rot"], tg["rel_obj_trans"],
+                                                        self.templates, obj_cls)
+            om = {"ADDS": adds, "MCE": mce, "OCE": oce, "MME": mme}
+        else:
+            used = None
+            om = obj_metrics(out["obj_rot_out"], out["obj_trans_out"], tg["obj_rot"], tg["rel_obj_trans"],
+                             self.templates[obj_cls], ho3d)
+        self.total += B
+        if ho3d:                                                                  # main/test.py:133-176
+            if cfg.use_inverse_kinematics:
+                joints, mesh = out["ik_joints_out"], out["ik_verts_out"]
+            else:
+                joints, mesh = out["mano_joints_out"], out["mano_mesh_out"]
+            joints = (joints + root[:, None]) @ self.coord_change
+            mesh = (mesh + root[:, None]) @ self.coord_change
+            self._add({"ADDS_error": om["ADDS"], "MME_error": om["MME"]}, B, used)
+            if self.native:                                                       # read back in write()
+                self.joint_list.append(joints[:, JOINTS_SIMPLE_TO_MANO])
+                self.mesh_list.append(mesh)
+            else:
+                self.joint_list += [j[JOINTS_SIMPLE_TO_MANO] for j in joints.cpu().numpy()]
+                self.mesh_list += list(mesh.cpu().numpy())
+            return
+        if cfg.use_inverse_kinematics:                                            # main/test.py:178-225
+            pj, gj = out["ik_joints_out"] - out["ik_joints_out"][:, :1], tg["joint_cam_no_trans"] / 1000
+        else:
+            pj, gj = out["mano_joints_out"], out["mano_joints_gt_out"]
+        mje, pamje = ops.eval_hand_joints(pj, gj)[:2] if self.native else eval_hand_joint(pj, gj)
+        self._add({"ADDS_error": om["ADDS"], "mano_mje": mje, "mano_pamje": pamje, "OCE_error": om["OCE"], "MCE_error": om["MCE"]}, B, used)
+        if cfg.eval_mesh and "mano_mesh_out" in out:
+            pv, gv = out["mano_mesh_out"], out["mano_mesh_gt_out"]
+            if self.native:
+                if self._fth is None:
+                    self._fth = ops.eval_thresholds(self.f_threshs, dev)
+                d0, d1, f0, f1, _ = ops.eval_mesh(pv, gv, self._fth)
+                self.mesh_err.feed_dist(d0)
+                self.mesh_err_al.feed_dist(d1)
+                self.f_score.append(f0)
+                self.f_score_al.append(f1)
+            else:
+                al = rigid_align(pv, gv)
+                self.mesh_err.feed(gv, pv)
+                self.mesh_err_al.feed(gv, al)
+                self.f_score.append(torch.stack([fscore(gv, pv, t) for t in self.f_threshs], 1).cpu().numpy())
+                self.f_score_al.append(torch.stack([fscore(gv, al, t) for t in self.f_threshs], 1).cpu().numpy())
+
+    def write(self, out_dir: str) -> str:
+        """results.txt (and, for ho3d, pred_mano.json) under out_dir -> the path of results.txt"""
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, "results.txt")
+        results = self.results
+        if self.native:                                        # the one read-back of the running sums
+            *vals, n_used = self._acc.tolist()
+            # a sample whose object was not evaluated (obj_cls < 0: HO3D's 019_pitcher_base, common/metrics.py:131-149) added zeros:
+            # the object keys are means over the evaluated samples, as the reference takes them; write_results divides by self.total
+            obj_scale = self.total / n_used if n_used > 0 else 0.0
+            results = {k: v * 100 * (obj_scale if k.endswith("_error") else 1.0) for k, v in zip(results, vals)}
+        if not self.ho3d and self.cfg.eval_mesh and self.f_score:
+            if self.native:
+                fs, fa = torch.cat(self.f_score).cpu().numpy(), torch.cat(self.f_score_al).cpu().numpy()
+            else:
+                fs, fa = np.concatenate(self.f_score), np.concatenate(self.f_score_al)
+            write_results(path, results, self.total, mesh=(self.mesh_err, self.mesh_err_al), fscores=(fs.T, fa.T, self.f_threshs))
+        else:
+            write_results(path, results, self.total)
+        if self.ho3d:
+            if self.native:
+                joints = list(torch.cat(self.joint_list).cpu().numpy()) if self.joint_list else []
+                meshes = list(torch.cat(self.mesh_list).cpu().numpy()) if self.mesh_list else []
+            else:
+                joints, meshes = self.joint_list, self.mesh_list
+            dump_pred_mano(os.path.join(out_dir, "pred_mano.json"), joints, meshes)
+            self.n_dumped = (len(joints), len(meshes))
+        return path

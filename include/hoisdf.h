@@ -952,6 +952,54 @@ typedef struct {
 int hoisdf_adamw_step(const hoisdf_adamw_chunk* chunks, int n_chunks, double lr, double beta1, double beta2,
                       double eps, double weight_decay, long step, float grad_scale, void* stream);
 
+/* ---- evaluation metrics: what main/test.py writes into results.txt, from device predictions ------------------------------
+ * reference: common/metrics.py:62-232 (object and hand-joint metrics, the similarity alignment), common/eval_util.py:11-136
+ * (EvalUtil.feed / get_measures, the F-score) as main/test.py:65-261 applies them.  csrc/eval.hip.  fp32 coordinates in metres
+ * in; distances are dx^2 + dy^2 + dz^2 directly; no float atomics and one fixed order per sum: two calls give the same bits.
+ * Every entry checks its arguments before any launch (HOISDF_ERR_INVALID names the argument); B = 0 returns 0, nothing launched.
+ * hoisdf_eval_workspace_bytes(B, V): bytes of `workspace` that any entry below needs for B samples of V vertices (pure host
+ *   arithmetic, -1 on B < 0 or V <= 0).  hoisdf_eval_accum_state_bytes(V, steps): bytes of an accumulator state (-1 on V <= 0
+ *   or steps outside 2 .. 65535, the range every accumulator entry accepts).
+ * hoisdf_eval_object (2 launches): obj_rot / obj_trans [B][P][3] = the P per-point predictions of a sample (axis-angle,
+ *   translation), averaged over P; obj_rot_gt / obj_trans_gt [B][3]; both rotations through the quaternion Rodrigues form with
+ *   the reference's + 1e-8; templates [T][V][3], obj_ids [B] int32 = the template of each sample.  Per sample, all four always:
+ *   adds = mean over PREDICTED vertices of the distance to the nearest target vertex, mce = mean distance of the 8 axis-aligned
+ *   bounding-box corners (corner order of common/metrics.py:70-72), oce = |trans - trans_gt|, mme = mean distance of
+ *   corresponding vertices; used [B] = 1.  A sample with obj_ids[b] < 0 (HO3D's 019_pitcher_base rule, metrics.py:131-143) or
+ *   >= T is not evaluated: its four outputs are 0 and used = 0.
+ * hoisdf_eval_hand_joints (1 launch): pred / gt [B][J][3]; mje [B] = mean distance of corresponding points, pamje [B] = the same
+ *   after the similarity (scale, rotation, translation) alignment of pred onto gt: fp64 centroids, H = (A-ca)^T (B-cb) / n and
+ *   varP from the fp32 inputs, a Jacobi SVD of H with descending singular values, the reflection rule of metrics.py:195-198
+ *   (det(V U^T) < 0: last singular value and last row of V^T negated), c = sum(s) / varP, t = cb - c R ca.  aligned_out
+ *   [B][J][3] (may be NULL) = the aligned points rounded to fp32; transform_out [B][13] doubles (may be NULL) = c, R row-major,
+ *   t; dist_out / dist_aligned_out [B][J] (each may be NULL) = the per-point distances before / after the alignment.  A rank-deficient H (collinear or coplanar points) takes one of the equally good rotations; pred points that are all
+ *   equal (varP = 0) get c = 0.
+ * hoisdf_eval_mesh (3 launches): pred / gt [B][V][3] meshes with corresponding vertices, thresholds [n_thresh] DEVICE doubles
+ *   (1 <= n_thresh <= 16).  dist_raw / dist_aligned [B][V] = per-vertex distances before / after the alignment above (what the
+ *   accumulator is fed); fscore / fscore_aligned [B][n_thresh] = eval_util.py:117-136 on brute-force nearest neighbours
+ *   (precision = share of gt vertices with a pred vertex nearer than th, recall = the other way round, 2pr / (p + r), 0 when
+ *   p + r = 0; fp32 distance compared in fp64, integer counts); aligned_out [B][V][3] may be NULL.
+ * hoisdf_eval_accum_init / _feed / _finish: EvalUtil for fully visible meshes.  state = hoisdf_eval_accum_state_bytes(V, steps)
+ *   device bytes, zeroed by _init: the number of samples fed, one fp64 sum per vertex, one uint32 count per (threshold,
+ *   vertex) of d <= th (fp32 distance compared in fp64).  thresholds [steps] DEVICE doubles, the same array for every feed and
+ *   the finish.  _feed adds dist [B][V]; one thread owns a vertex and walks the samples in order, so feeding 3 + 3 samples
+ *   and feeding 6 leave the same bits.  _finish writes out [2 + steps] DEVICE doubles: the mean EPE, the AUC (trapezoid of the
+ *   per-threshold PCK over the thresholds, normalised by their range, mean over vertices) and the PCK curve; NaN before the
+ *   first feed.  The median EPE of get_measures is not provided (it needs every distance; results.txt does not print it). */
+long hoisdf_eval_workspace_bytes(int B, int V);
+long hoisdf_eval_accum_state_bytes(int V, int steps);
+int hoisdf_eval_object(const float* obj_rot, const float* obj_trans, int P, const float* obj_rot_gt, const float* obj_trans_gt,
+                       const float* templates, int T, int V, const int32_t* obj_ids, int B, float* adds, float* mce, float* oce,
+                       float* mme, int32_t* used, void* workspace, long workspace_bytes, void* stream);
+int hoisdf_eval_hand_joints(const float* pred, const float* gt, int B, int J, float* mje, float* pamje, float* aligned_out,
+                            double* transform_out, float* dist_out, float* dist_aligned_out, void* stream);
+int hoisdf_eval_mesh(const float* pred, const float* gt, int B, int V, const double* thresholds, int n_thresh, float* dist_raw,
+                     float* dist_aligned, float* fscore, float* fscore_aligned, float* aligned_out, void* workspace,
+                     long workspace_bytes, void* stream);
+int hoisdf_eval_accum_init(void* state, int V, int steps, void* stream);
+int hoisdf_eval_accum_feed(void* state, const float* dist, int B, int V, const double* thresholds, int steps, void* stream);
+int hoisdf_eval_accum_finish(const void* state, int V, const double* thresholds, int steps, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,15 +11,13 @@ HO3D-shaped synthetic samples against synthetic object templates (the numbers ar
 import argparse
 import os
 
-import numpy as np
 import torch
 
 from hoisdf_amd import metrics as M
 from hoisdf_amd.config import cfg
 from hoisdf_amd.engine import SyntheticDataset, Tester
 
-# data/ho3d.py:47-70: jointsMapSimpleToMano = argsort(jointsMapManoToSimple) - the order of the HO3D submission file
-JOINTS_SIMPLE_TO_MANO = [0, 5, 6, 7, 9, 10, 11, 17, 18, 19, 13, 14, 15, 1, 2, 3, 4, 8, 12, 16, 20]
+JOINTS_SIMPLE_TO_MANO = M.JOINTS_SIMPLE_TO_MANO            # the order of the HO3D submission file
 
 
 def parse_args():
@@ -36,6 +34,8 @@ def parse_args():
                     help="with --native-infer: the image encoder too through the C ABI (hoisdf_encoder_infer, cfg.native_encoder)")
     ap.add_argument("--native-ik", action="store_true",
                     help="the IK variant's closed-form post-process as one HIP launch (hoisdf_ik_mano_fwd, cfg.native_ik)")
+    ap.add_argument("--native-metrics", action="store_true",
+                    help="the evaluation metrics through the hoisdf_eval_* entries, running sums on the device (cfg.native_metrics)")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -50,6 +50,7 @@ def main():
     cfg.native_infer = bool(a.native_infer)
     cfg.native_encoder = bool(a.native_encoder)
     cfg.native_ik = bool(a.native_ik)
+    cfg.native_metrics = bool(a.native_metrics)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
@@ -62,62 +63,15 @@ def main():
     g = torch.Generator().manual_seed(0)
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
-    results = {"ADDS_error": 0.0}
-    if ho3d:
-        results["MME_error"] = 0.0
-        coord_change = torch.tensor([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]], device=dev)
-        joint_list, mesh_list = [], []
-    else:
-        results.update(mano_mje=0.0, mano_pamje=0.0, OCE_error=0.0, MCE_error=0.0)
-        mesh_err, mesh_err_al = M.MeshEval(), M.MeshEval()
-        f_score, f_score_al, f_threshs = [], [], [0.005, 0.015]
-    total = 0
+    ev = M.Evaluator(cfg, templates, native=M.native_metrics_enabled(cfg))
     for it, (inputs, targets, meta) in enumerate(loader):
         out = tester.predict(inputs, targets, meta, mano_layer=mano_layer)
         B = meta["mano_root"].shape[0]
-        tg = {k: v.to(dev) for k, v in targets.items()}
-        root = meta["mano_root"].to(dev)
-        obj_cls = (torch.arange(B) + it) % templates.shape[0]
-        om = M.obj_metrics(out["obj_rot_out"], out["obj_trans_out"], tg["obj_rot"], tg["rel_obj_trans"], templates[obj_cls], ho3d)
-        total += B
-        results["ADDS_error"] += om["ADDS"] * B * 100
-        if ho3d:                                                                  # main/test.py:133-176
-            if cfg.use_inverse_kinematics:
-                joints, mesh = out["ik_joints_out"], out["ik_verts_out"]
-            else:
-                joints, mesh = out["mano_joints_out"], out["mano_mesh_out"]
-            joints = (joints + root[:, None]) @ coord_change
-            mesh = (mesh + root[:, None]) @ coord_change
-            results["MME_error"] += om["MME"] * B * 100
-            joint_list += [j[JOINTS_SIMPLE_TO_MANO] for j in joints.cpu().numpy()]
-            mesh_list += list(mesh.cpu().numpy())
-        else:                                                                     # main/test.py:178-225
-            if cfg.use_inverse_kinematics:
-                mje, pamje = M.eval_hand_joint(out["ik_joints_out"] - out["ik_joints_out"][:, :1], tg["joint_cam_no_trans"] / 1000)
-            else:
-                mje, pamje = M.eval_hand_joint(out["mano_joints_out"], out["mano_joints_gt_out"])
-            results["mano_mje"] += mje * B * 100
-            results["mano_pamje"] += pamje * B * 100
-            results["OCE_error"] += om["OCE"] * B * 100
-            results["MCE_error"] += om["MCE"] * B * 100
-            if cfg.eval_mesh and "mano_mesh_out" in out:
-                pv, gv = out["mano_mesh_out"], out["mano_mesh_gt_out"]
-                al = M.rigid_align(pv, gv)
-                mesh_err.feed(gv, pv)
-                mesh_err_al.feed(gv, al)
-                f_score.append(torch.stack([M.fscore(gv, pv, t) for t in f_threshs], 1).cpu().numpy())
-                f_score_al.append(torch.stack([M.fscore(gv, al, t) for t in f_threshs], 1).cpu().numpy())
+        ev.feed(out, targets, meta, (torch.arange(B) + it) % templates.shape[0])
     out_dir = a.out_dir or (os.path.dirname(a.ckpt_path) if a.ckpt_path else "outputs/result")
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "results.txt")
-    if not ho3d and cfg.eval_mesh and f_score:
-        M.write_results(path, results, total, mesh=(mesh_err, mesh_err_al),
-                        fscores=(np.concatenate(f_score).T, np.concatenate(f_score_al).T, f_threshs))
-    else:
-        M.write_results(path, results, total)
+    path = ev.write(out_dir)
     if ho3d:
-        M.dump_pred_mano(os.path.join(out_dir, "pred_mano.json"), joint_list, mesh_list)
-        print(f"Dumped {len(joint_list)} joints and {len(mesh_list)} verts predictions to {out_dir}/pred_mano.json")
+        print(f"Dumped {ev.n_dumped[0]} joints and {ev.n_dumped[1]} verts predictions to {out_dir}/pred_mano.json")
     print(open(path).read())
 
 
