@@ -156,6 +156,28 @@ class PoseOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _POSE_OUT]
 
 
+CROP_MAX_POINTS = 32
+
+
+class Crop(C.Structure):
+    """include/hoisdf.h hoisdf_crop"""
+    _fields_ = [("affine", C.c_float * 9), ("post_rot_trans", C.c_float * 9), ("rot_mat", C.c_float * 9), ("inverse", C.c_double * 6),
+                ("K", C.c_double * 9), ("bbox_hand", C.c_double * 4), ("bbox_obj", C.c_double * 4), ("n_joints", C.c_int),
+                ("n_corners", C.c_int), ("flip", C.c_int), ("reserved", C.c_int), ("joints_uv", C.c_double * 2 * CROP_MAX_POINTS),
+                ("p2d", C.c_double * 2 * CROP_MAX_POINTS)]
+
+
+class Frame(C.Structure):
+    """include/hoisdf.h hoisdf_frame"""
+    _fields_ = [("frame", C.c_void_p), ("hand_mask", C.c_void_p), ("obj_mask", C.c_void_p), ("H", C.c_int), ("W", C.c_int),
+                ("mask_packed", C.c_int), ("reserved", C.c_int)]
+
+
+class Photo(C.Structure):
+    """include/hoisdf.h hoisdf_photo"""
+    _fields_ = [("blur_sigma", C.c_float), ("factor", C.c_float * 4), ("enabled", C.c_int), ("order", C.c_int * 4)]
+
+
 _P, _I, _L, _F, _U64, _D = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_double
 _PYR = C.POINTER(Pyramid)
 _SDFW = C.POINTER(SdfWeights)
@@ -261,6 +283,11 @@ SIGNATURES: Dict[str, List] = {
     "hoisdf_eval_accum_init": [_P, _I, _I, _P],
     "hoisdf_eval_accum_feed": [_P, _P, _I, _I, _P, _I, _P],
     "hoisdf_eval_accum_finish": [_P, _I, _P, _I, _P, _P],
+    "hoisdf_crop_params_dexycb": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "hoisdf_crop_params_ho3d": [_P, _P, _I, _P, _I, _I, _I, _I, _P],
+    "hoisdf_aug_params_dexycb": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _D, _P, _D, _D, _P],
+    "hoisdf_image_crop": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hoisdf_image_augment": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 _RET = {"hoisdf_version": C.c_char_p, "hoisdf_last_error": C.c_char_p}
 _OTHER = {"hoisdf_set_deterministic": ([_I], None), "hoisdf_set_gemm_emu": ([_I], None), "hoisdf_get_gemm_emu": ([], C.c_int), "hoisdf_get_deterministic": ([], C.c_int),

@@ -53,6 +53,10 @@ class Config:
     # not in the reference: on that path (eval, no gradient, native_infer on) the image encoder too runs through the C ABI
     # (hoisdf_encoder_infer: BatchNorm folded, exact-f32 HIP convolutions) instead of torch / MIOpen (HOISDF_ENCODER=native does the same)
     native_encoder = False
+    # not in the reference: batches that carry raw camera frames (uint8 frame, two masks, 2D labels) are cropped / augmented on the
+    # device (hoisdf_amd/image_data.py ImagePipeline: hoisdf_image_crop / hoisdf_image_augment) instead of arriving as ready
+    # tensors from a CPU loader.  Also HOISDF_IMAGE=native / test.py --native-image
+    native_image = False
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

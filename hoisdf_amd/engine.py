@@ -22,6 +22,7 @@ import os.path as osp
 import re
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -95,9 +96,17 @@ class SyntheticSdfDataset(torch.utils.data.Dataset):
         return ins, tg, mt
 
 
+RAW_FRAME_SHAPE = (480, 640)          # the reference's camera frames (H, W)
+
+
 class SyntheticDataset(torch.utils.data.Dataset):
-    def __init__(self, cfg: Config, length: int = 64, seed: int = 0):
-        self.cfg, self.length, self.seed = cfg, length, seed
+    """``raw_frames=True``: a sample shaped like the reference's BEFORE its crop - inputs carry ``frame`` (uint8 [480][640][3]),
+    ``hand_mask`` / ``obj_mask`` (uint8 [480][640]) instead of ``img``; meta_info carries the raw frame's ``joints_uv_raw`` (21, 2)
+    float32, ``p2d_raw`` (21, 2) float64, ``cam_intr_raw`` and ``do_flip`` instead of ``cam_intr`` / ``bbox_hand`` / ``bbox_obj``;
+    targets lack ``hand_seg`` / ``obj_seg`` / ``joint_coord``.  ``ImagePipeline`` (cfg.native_image) produces what is missing."""
+
+    def __init__(self, cfg: Config, length: int = 64, seed: int = 0, raw_frames: bool = False):
+        self.cfg, self.length, self.seed, self.raw_frames = cfg, length, seed, raw_frames
 
     def __len__(self):
         return self.length
@@ -105,7 +114,58 @@ class SyntheticDataset(torch.utils.data.Dataset):
     def __getitem__(self, i):
         ins, tg, mt = T.synthetic_batch(1, self.cfg.num_samp_hand, self.cfg.num_samp_obj, seed=self.seed * 100003 + i)
         sq = lambda d: {k: v[0] for k, v in d.items()}
-        return sq(ins), sq(tg), sq(mt)
+        ins, tg, mt = sq(ins), sq(tg), sq(mt)
+        if self.raw_frames:
+            H, W = RAW_FRAME_SHAPE
+            g = torch.Generator().manual_seed(self.seed * 104729 + i)
+            ins.pop("img")
+            for k in ("hand_seg", "obj_seg", "joint_coord"):
+                tg.pop(k)
+            for k in ("cam_intr", "bbox_hand", "bbox_obj"):
+                mt.pop(k)
+            ins["frame"] = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8)
+            c = torch.tensor([W / 2.0, H / 2.0]) + 60 * (torch.rand(2, generator=g) - 0.5)
+            mt["joints_uv_raw"] = c + 70 * (torch.rand(21, 2, generator=g) - 0.5)
+            mt["p2d_raw"] = (c + torch.tensor([30.0, 10.0]) + 60 * (torch.rand(21, 2, generator=g) - 0.5)).double()
+            yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+            ins["hand_mask"] = (((xx - c[0]) ** 2 + (yy - c[1]) ** 2) < 45 ** 2).to(torch.uint8)
+            ins["obj_mask"] = (((xx - c[0] - 30).abs() < 35) & ((yy - c[1] - 10).abs() < 30)).to(torch.uint8)
+            mt["cam_intr_raw"] = torch.tensor([[600.0, 0, W / 2.0 - 8], [0, 600.0, H / 2.0 + 1], [0, 0, 1]])
+            mt["do_flip"] = torch.rand(1, generator=g)[0] < 0.5
+        return ins, tg, mt
+
+
+def native_image_enabled(cfg: Config) -> bool:
+    """cfg.native_image (default False) or HOISDF_IMAGE=native"""
+    return bool(getattr(cfg, "native_image", False)) or os.environ.get("HOISDF_IMAGE", "") == "native"
+
+
+def apply_image_pipeline(pipe, inputs, targets, meta, rng=None, draws=None):
+    """A raw-frame batch (SyntheticDataset(raw_frames=True)) through ``ImagePipeline``: the dicts gain, in place, what the reference's
+    loader would have delivered - ``img`` (a channels_last view of the NHWC crop, no copy), ``hand_seg`` / ``obj_seg`` /
+    ``joint_coord``, ``cam_intr`` / ``bbox_hand`` / ``bbox_obj`` / ``p2d`` - and, for a training batch (``rng`` given), the 3D labels
+    turned by the augmentation and ``aug_rot`` / ``do_flip`` for ``SdfStore.make_inputs``.  Returns the pipeline's output."""
+    B = inputs["frame"].shape[0]
+    labels = []
+    for b in range(B):
+        lab = dict(joints_uv=meta["joints_uv_raw"][b].cpu().numpy(), p2d=meta["p2d_raw"][b].cpu().numpy(),
+                   K=meta["cam_intr_raw"][b].double().cpu().numpy(), flip=bool(meta["do_flip"][b]))
+        if rng is not None:                 # (the synthetic 3D labels are already those of the mirrored frame: only the rotation applies)
+            lab.update(flip_3d=False, joints_3d=targets["joint_cam_no_trans"][b], mano_param=targets["mano_param"][b], obj_rot=targets["obj_rot"][b],
+                       obj_trans=targets["rel_obj_trans"][b])
+        labels.append(lab)
+    frames, masks = inputs.pop("frame"), (inputs.pop("hand_mask"), inputs.pop("obj_mask"))
+    if rng is None:
+        out = pipe.eval_batch(frames, masks, labels)
+    else:
+        out = pipe.train_batch(frames, masks, labels, rng, draws)
+        targets.update(joint_cam_no_trans=out["joints_3d"], mano_param=out["mano_param"], obj_rot=out["obj_rot"],
+                       rel_obj_trans=out["obj_trans"])
+        meta["aug_rot"] = out["rot_mat"]
+    inputs["img"] = out["img"].permute(0, 3, 1, 2)
+    targets.update(hand_seg=out["hand_seg"], obj_seg=out["obj_seg"], joint_coord=out["joint_coord"])
+    meta.update(cam_intr=out["cam_intr"], bbox_hand=out["bbox_hand"], bbox_obj=out["bbox_obj"], p2d=out["p2d"])
+    return out
 
 
 def reserve_hbm_pool(model: torch.nn.Module, fraction: float = 0.5, device=None) -> int:
@@ -222,6 +282,13 @@ class Trainer:
 
     def train_step(self, inputs, targets, meta, epoch: int, batch_ratio: float):
         dev = self.device
+        if "frame" in inputs and native_image_enabled(self.cfg):
+            from .image_data import ImagePipeline
+            if getattr(self, "_image_pipeline", None) is None:
+                self._image_pipeline = ImagePipeline(self.cfg, dev, nchw=False)
+            self._image_draws = getattr(self, "_image_draws", 0) + 1
+            rng = np.random.default_rng(_mix_seed(getattr(self, "_epoch_seed", self.base_seed), (1 << 20) + self._image_draws))
+            apply_image_pipeline(self._image_pipeline, inputs, targets, meta, rng)
         inputs, targets, meta = (T.to_device(x, dev) for x in (inputs, targets, meta))
         if self.sdf_store is not None and "sdf_frame" in meta:
             c = self.cfg
@@ -286,6 +353,11 @@ class Tester:
         ``cfg.native_ik`` / ``HOISDF_IK=native`` the post-process is one HIP launch (hoisdf_ik_mano_fwd) - the last launch of
         hoisdf_pose_infer itself when native inference is on as well."""
         from .ik import ik_solver_mano, ik_solver_mano_native, native_ik_enabled
+        if "frame" in inputs and native_image_enabled(self.cfg):
+            from .image_data import ImagePipeline
+            if getattr(self, "_image_pipeline", None) is None:
+                self._image_pipeline = ImagePipeline(self.cfg, self.device, nchw=False)      # NHWC: what hoisdf_encoder_infer reads
+            apply_image_pipeline(self._image_pipeline, inputs, targets, meta)
         inputs, targets, meta = (T.to_device(x, self.device) for x in (inputs, targets, meta))
         ik = self.cfg.use_inverse_kinematics and mano_layer is not None
         native = ik and native_ik_enabled(self.cfg)

@@ -1000,6 +1000,78 @@ int hoisdf_eval_accum_init(void* state, int V, int steps, void* stream);
 int hoisdf_eval_accum_feed(void* state, const float* dist, int B, int V, const double* thresholds, int steps, void* stream);
 int hoisdf_eval_accum_finish(const void* state, int V, const double* thresholds, int steps, double* out, void* stream);
 
+/* ---- image preparation: from a camera frame to the model input --------------------------------------------------------------
+ * reference: the image half of Dataset.__getitem__ (data/dexycb.py:219-404 data_aug / data_crop, data/ho3d.py:399-427 data_crop,
+ * data/dataset_util.py get_bbox_joints, fuse_bbox, get_affine_transform, transform_coords, transform_img, color_jitter).
+ * csrc/imgprep_params.c (host arithmetic, no GPU call) and csrc/imgprep.hip (kernels); hoisdf_amd/image_oracle.py restates both.
+ *
+ * hoisdf_crop_params_dexycb / _ho3d / hoisdf_aug_params_dexycb fill a hoisdf_crop on the host.  Number formats are the
+ *   reference's: boxes of float32 joints and the evaluation affine are float32 arithmetic, the rest float64; affine,
+ *   post_rot_trans and rot_mat are the float32 matrices get_affine_transform returns; `inverse` = the first two rows of the
+ *   float64 inverse of that float32 affine.  joints_uv [n_joints][2] float32 and p2d [n_corners][2] float64 are the labels of the
+ *   RAW frame (at most HOISDF_CROP_MAX_POINTS each); K [9] row-major; flip != 0 (a left hand) mirrors them first
+ *   (u -> W - u - 1, K[0][2] -> W - K[0][2] - 1) and the warp then reads the raw frame mirrored.  res = input_img_shape[0],
+ *   hm = output_hm_shape[0].  Out: K = K' (dexycb: post_rot_trans . K, ho3d: affine . K), bbox_hand / bbox_obj in crop pixels,
+ *   joints_uv at heat-map scale, p2d normalised to bbox_obj.  The training variant takes the random numbers as arguments:
+ *   centre offset = center_jittering * scale * center_u[0..1], scale *= scale_jitter, rotation `rot` in radians.
+ *   HOISDF_ERR_INVALID: null pointer, point counts outside 1 .. HOISDF_CROP_MAX_POINTS, res / hm / frame size <= 0, a
+ *   degenerate (empty or non-finite) fused box.
+ * hoisdf_image_crop (evaluation, 1 launch per 16 samples): frames[b] describes sample b's DEVICE buffers: frame u8 [H][W][3],
+ *   hand_mask / obj_mask u8 [H][W] bytes or, mask_packed != 0, bits as numpy.packbits leaves them (bit 7 of byte 0 first).
+ *   crops [B] is HOST memory (inverse and flip are read).  Output pixel (x, y) takes source pixel
+ *   (floor(t00 (x + .5) + t01 (y + .5) + t02), floor(t10 (x + .5) + t11 (y + .5) + t12)) evaluated in float64 without fused
+ *   multiply-add, 0 outside the frame (PIL's Image.AFFINE with its default nearest filter).  img = level / 255 as float32,
+ *   [B][res][res][3] (nchw = 0, what hoisdf_encoder_infer consumes) or [B][3][res][res]; crop_u8 [B][res][res][3] may be NULL;
+ *   hand_seg / obj_seg [B][hm][hm] float32: heat-map pixel i reads crop pixel floor((i + .5) res / hm) of the same map (the
+ *   NEAREST resize folded in, no res x res mask is written).
+ * hoisdf_image_augment (training): the same warp into crop_u8 (required), then per sample photo[b] (HOST memory): a separable
+ *   7-tap Gaussian blur of sigma blur_sigma (edges replicated, rounded to the nearest level, the identity below 0.05), then the
+ *   enabled ones of brightness (0), contrast (1), saturation (2), hue (3) in the order `order` gives, each leaving integer levels
+ *   0 .. 255: out = trunc(clip(deg + f (x - deg), 0, 255)) in float32 with deg = 0, int(mean(L) + .5) over the crop, L per pixel;
+ *   L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16; hue = PIL's RGB -> HSV, H += uint8(factor 255) modulo 256, HSV -> RGB.
+ *   lsum [B] uint32 DEVICE: the integer sum of L the contrast of sample b saw (integer atomics: order-independent; 0 when contrast
+ *   is off).  Launches per 16 samples: the warp; a memset of lsum; when any sample has a contrast, the chain up to it; the chain.
+ * Both only enqueue on `stream`, check every argument before the first launch (HOISDF_ERR_INVALID: null pointer, res / hm <= 0,
+ *   res % hm != 0, frame size <= 0, a singular or non-finite inverse, enabled bits outside 0 .. 15, an order that is no
+ *   permutation of 0 .. 3, a negative or non-finite blur_sigma / factor) and return 0 for B = 0. */
+#define HOISDF_CROP_MAX_POINTS 32
+typedef struct {
+  float affine[9];
+  float post_rot_trans[9];
+  float rot_mat[9];
+  double inverse[6];
+  double K[9];
+  double bbox_hand[4];
+  double bbox_obj[4];
+  int n_joints, n_corners, flip, reserved;
+  double joints_uv[HOISDF_CROP_MAX_POINTS][2];
+  double p2d[HOISDF_CROP_MAX_POINTS][2];
+} hoisdf_crop;
+typedef struct {
+  const uint8_t* frame;
+  const uint8_t* hand_mask;
+  const uint8_t* obj_mask;
+  int H, W;
+  int mask_packed, reserved;
+} hoisdf_frame;
+typedef struct {
+  float blur_sigma;
+  float factor[4];
+  int enabled;       /* bit i: op i is present */
+  int order[4];
+} hoisdf_photo;
+int hoisdf_crop_params_dexycb(const float* joints_uv, int n_joints, const double* p2d, int n_corners, const double* K, int frame_w,
+                              int frame_h, int flip, int res, int hm, hoisdf_crop* out);
+int hoisdf_crop_params_ho3d(const double* bbox_hand, const double* p2d, int n_corners, const double* K, int frame_w, int frame_h,
+                            int res, int hm, hoisdf_crop* out);
+int hoisdf_aug_params_dexycb(const float* joints_uv, int n_joints, const double* p2d, int n_corners, const double* K, int frame_w,
+                             int frame_h, int flip, int res, int hm, double center_jittering, const double* center_u,
+                             double scale_jitter, double rot, hoisdf_crop* out);
+int hoisdf_image_crop(const hoisdf_frame* frames, const hoisdf_crop* crops, int B, int res, int hm, int nchw, float* img,
+                      uint8_t* crop_u8, float* hand_seg, float* obj_seg, void* stream);
+int hoisdf_image_augment(const hoisdf_frame* frames, const hoisdf_crop* crops, const hoisdf_photo* photo, int B, int res, int hm,
+                         int nchw, float* img, uint8_t* crop_u8, uint32_t* lsum, float* hand_seg, float* obj_seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ import torch
 
 from hoisdf_amd import metrics as M
 from hoisdf_amd.config import cfg
-from hoisdf_amd.engine import SyntheticDataset, Tester
+from hoisdf_amd.engine import SyntheticDataset, Tester, native_image_enabled
 
 JOINTS_SIMPLE_TO_MANO = M.JOINTS_SIMPLE_TO_MANO            # the order of the HO3D submission file
 
@@ -32,6 +32,8 @@ def parse_args():
                     help="run everything after the image encoder through the one C entry hoisdf_pose_infer (cfg.native_infer)")
     ap.add_argument("--native-encoder", action="store_true",
                     help="with --native-infer: the image encoder too through the C ABI (hoisdf_encoder_infer, cfg.native_encoder)")
+    ap.add_argument("--native-image", action="store_true",
+                    help="raw synthetic camera frames, cropped on the device (hoisdf_image_crop, cfg.native_image)")
     ap.add_argument("--native-ik", action="store_true",
                     help="the IK variant's closed-form post-process as one HIP launch (hoisdf_ik_mano_fwd, cfg.native_ik)")
     ap.add_argument("--native-metrics", action="store_true",
@@ -50,6 +52,7 @@ def main():
     cfg.native_infer = bool(a.native_infer)
     cfg.native_encoder = bool(a.native_encoder)
     cfg.native_ik = bool(a.native_ik)
+    cfg.native_image = bool(a.native_image)
     cfg.native_metrics = bool(a.native_metrics)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
@@ -59,7 +62,7 @@ def main():
     if mano_layer is None:
         from hoisdf_amd.nets.mano import ManoLayer
         mano_layer = ManoLayer().to(dev)
-    loader = torch.utils.data.DataLoader(SyntheticDataset(cfg, a.batch * a.n_batches, seed=1), batch_size=a.batch)
+    loader = torch.utils.data.DataLoader(SyntheticDataset(cfg, a.batch * a.n_batches, seed=1, raw_frames=native_image_enabled(cfg)), batch_size=a.batch)
     g = torch.Generator().manual_seed(0)
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
