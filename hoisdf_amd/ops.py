@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (_DEC_W, _SDF_G, MLP_MAX_LAYERS, DecoderLayerDesc, DecoderLayerGrads, DecoderLayerWeights, EncoderLayerDesc,
+from ._lib import (MLP_MAX_LAYERS, DecoderLayerDesc, DecoderLayerGrads, DecoderLayerWeights, EncoderLayerDesc,
                    EncoderLayerGrads, EncoderLayerWeights, Mlp, MlpGrads, PoseOutputs, Pyramid, SdfWeightGrads, SdfWeights, call, lib)
 from .emu_images import WeightImageCache, prepare_batch_table
 
@@ -728,7 +728,7 @@ class _SdfQueryTrain(torch.autograd.Function):
         dev = pts.device
         n, Cc = pts.shape[0], w.C
         parts = _zero_views([512 * Cc, 512, 256 * 512, 256, 512 * 292, 512, 224 * 512, 224, 512 * 516, 512, 512 * 512, 512, 512, 1], dev)
-        G = SdfWeightGrads(**{k: t.data_ptr() for k, t in zip(_SDF_G, parts)})
+        G = SdfWeightGrads(*[t.data_ptr() for t in parts])
         if acc is not None:
             grads = acc.bufs
             acc.flat.record_stream(torch.cuda.current_stream(dev))
@@ -1480,7 +1480,7 @@ class _EncoderLayerC(torch.autograd.Function):
         if xm is not None and xm[2] == x._version:
             d.x_mag = xm[0]
             ctx.x_mag_owner = xm[1]
-        w = EncoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_ENC_W_NAMES, params)})
+        w = EncoderLayerWeights(*[t.data_ptr() for t in params])       # positional = the header's field order: parameters, then images
         _EncoderLayerC._images(w, (w_in, w_out, w1, w2), False, B * nq, B * S, E, nq == S)
         dp, wp = C.addressof(d), C.addressof(w)
         n_saved = lib().hoisdf_encoder_layer_saved_bytes(dp) if d.training else 0
@@ -1508,8 +1508,8 @@ class _EncoderLayerC(torch.autograd.Function):
         dev = x.device
         # one zero slice for all parameter gradients
         parts = _zero_views([(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E], dev)
-        G = EncoderLayerGrads(**{"d" + n: t.data_ptr() for n, t in zip(_ENC_W_NAMES, parts)})
-        w = EncoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_ENC_W_NAMES, params)})
+        G = EncoderLayerGrads(*[t.data_ptr() for t in parts])
+        w = EncoderLayerWeights(*[t.data_ptr() for t in params])
         _EncoderLayerC._images(w, (w_in, w_out, w1, w2), True, B * nq, B * S, E, nq == S)
         dp = C.addressof(d)
         n_ws = lib().hoisdf_encoder_layer_workspace_bytes(dp, 1)
@@ -1522,7 +1522,6 @@ class _EncoderLayerC(torch.autograd.Function):
         return (dx, None, None, None, *parts, None, None)
 
 
-_ENC_W_NAMES = ("w_in", "b_in", "w_out", "b_out", "g1", "be1", "w1", "b1", "w2", "b2", "g2", "be2", "g3", "be3")
 _ENCODER_LAYER_C = True              # tests set it to False to compare the C entry against the per-op node
 
 
@@ -1548,14 +1547,14 @@ class _DecoderLayerC(torch.autograd.Function):
     def forward(ctx, tgt, memory, query_pos, mask_u8, kv_len, p, H, eps, *params):
         tgt, memory, query_pos = tgt.contiguous(), memory.contiguous(), query_pos.contiguous()
         _chk(tgt, memory, query_pos, *params)
-        assert len(params) == len(_DEC_W) and all(t.is_contiguous() for t in params) and mask_u8.dtype == torch.uint8
+        assert len(params) == len(DecoderLayerGrads._fields_) and all(t.is_contiguous() for t in params) and mask_u8.dtype == torch.uint8
         B, Q, E = tgt.shape
         S = memory.shape[1]
         F = params[8].shape[0]
         d = DecoderLayerDesc(B=B, Q=Q, S=S, E=E, F=F, H=H, kv_len=int(kv_len), eps=eps, drop_p=p, training=int(any(ctx.needs_input_grad)))
         for i in range(6):
             d.seed[i] = next_seed() if p > 0 else 0
-        w = DecoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_DEC_W, params)})
+        w = DecoderLayerWeights(*[t.data_ptr() for t in params])
         ca_w_in = params[4]
         if _GEMM_EMU and B * S >= _GEMM_EMU_MIN_ROWS:
             w.img_ca_kv = _emu_image(ca_w_in[E:], False).data_ptr()
@@ -1580,8 +1579,8 @@ class _DecoderLayerC(torch.autograd.Function):
         B, Q, S, E = d.B, d.Q, d.S, d.E
         dev = tgt.device
         *parts, d_qpos = _zero_views([t.shape for t in params] + [(Q, E)], dev)      # one zero slice: every parameter gradient + d query_pos
-        G = DecoderLayerGrads(**{"d" + n: t.data_ptr() for n, t in zip(_DEC_W, parts)})
-        w = DecoderLayerWeights(**{n: t.data_ptr() for n, t in zip(_DEC_W, params)})
+        G = DecoderLayerGrads(*[t.data_ptr() for t in parts])
+        w = DecoderLayerWeights(*[t.data_ptr() for t in params])
         if _GEMM_EMU and B * S >= _GEMM_EMU_MIN_ROWS:
             w.img_t_ca_kv = _emu_image(params[4][E:], True).data_ptr()
         dp = C.addressof(d)
@@ -1605,7 +1604,7 @@ def decoder_layer_ok(p, *tensors) -> bool:
 
 
 def decoder_layer(tgt, memory, query_pos, mask_u8, kv_len, p, H, eps, *params):
-    """-> (out (B,Q,E), y = the decoder stack's norm of out).  params in the order of _lib._DEC_W (self_attn in / out projection,
+    """-> (out (B,Q,E), y = the decoder stack's norm of out).  params in the order of hoisdf_decoder_layer_weights (self_attn in / out projection,
     multihead_attn in / out projection, linear1, linear2, norm1..3, stack norm); query_pos (Q,E) is broadcast over the batch."""
     return _DecoderLayerC.apply(tgt, memory, query_pos, mask_u8, int(kv_len), float(p), int(H), float(eps), *params)
 
