@@ -57,6 +57,16 @@ class Config:
     # device (hoisdf_amd/image_data.py ImagePipeline: hoisdf_image_crop / hoisdf_image_augment) instead of arriving as ready
     # tensors from a CPU loader.  Also HOISDF_IMAGE=native / test.py --native-image
     native_image = False
+    # not in the reference: "mesh" = the SDF query points and their two distances are computed on the device each step from the
+    # step's own hand and object meshes (hoisdf_amd/sdf_data.py MeshSdfSource: hoisdf_mesh_sdf_rows) instead of being read from
+    # precomputed sdf_processed rows.  "" = off.  Also HOISDF_SDF=mesh.  The sampling recipe is DeepSDF's near-surface one scaled to a
+    # hand (two Gaussian shells + a uniform share in the padded box); it is NOT fitted to the precomputed files' distribution
+    sdf_source = ""
+    mesh_sdf_sigma = (0.01, 0.003)       # metres: the two near-surface shells
+    mesh_sdf_uniform_every = 16          # every 16th candidate is uniform in the box (share 1/16)
+    mesh_sdf_pad = 0.05                  # metres around the mesh's bounding box
+    mesh_sdf_candidates = 4              # candidate rows per sample = this x num_samp_hand (num_samp_obj)
+    mesh_sdf_label_clamp = 0.05          # metres: a hand row keeps its part label where |sdf_hand| <= this
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

@@ -96,6 +96,28 @@ class SyntheticSdfDataset(torch.utils.data.Dataset):
         return ins, tg, mt
 
 
+class SyntheticMeshSdfDataset(torch.utils.data.Dataset):
+    """the dataset contract of ``Trainer(sdf_source=...)`` (``hoisdf_amd.sdf_data.MeshSdfSource``): no point sets and no SDF targets
+    at all - ``mano_param``, ``obj_rot``, ``rel_obj_trans`` (targets), ``mano_root``, ``obj_center_cam`` and ``obj_cls`` = the
+    object's template (meta_info) are what the points and their distances are computed from on the device, every step anew"""
+
+    def __init__(self, cfg: Config, n_templates: int, length: int = 64, seed: int = 0):
+        self.cfg, self.n_templates, self.length, self.seed = cfg, n_templates, length, seed
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, i):
+        ins, tg, mt = T.synthetic_batch(1, 1, 1, seed=self.seed * 100003 + i)
+        sq = lambda d: {k: v[0] for k, v in d.items()}
+        ins, tg, mt = sq(ins), sq(tg), sq(mt)
+        for k in ("hand_sdf_points", "obj_sdf_points", "hand_pre_points", "obj_pre_points"):
+            ins.pop(k)
+        tg.pop("hand_sdf"), tg.pop("obj_sdf")
+        mt["obj_cls"] = torch.tensor((self.seed + i) % self.n_templates)
+        return ins, tg, mt
+
+
 RAW_FRAME_SHAPE = (480, 640)          # the reference's camera frames (H, W)
 
 
@@ -225,9 +247,10 @@ def load_reference_state_dict(model: torch.nn.Module, network: Dict[str, torch.T
 
 class Trainer:
     def __init__(self, cfg: Config, device: torch.device, dataset=None, batch_size: Optional[int] = None,
-                 channels_last: bool = True, tune_encoder: bool = True, sdf_store=None):
+                 channels_last: bool = True, tune_encoder: bool = True, sdf_store=None, sdf_source=None):
         self.cfg, self.device = cfg, device
         self.sdf_store = sdf_store          # (f2) HBM-resident sdf_processed rows: the query points are drawn on the device
+        self.sdf_source = sdf_source        # no rows at all: points and distances computed from the batch's meshes (MeshSdfSource)
         self._sdf_draws = 0
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -255,8 +278,16 @@ class Trainer:
         self.lr_scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=cfg.lr_drop,
                                                             gamma=cfg.lr_decay_gamma)
         self.start_epoch = 0
+        if self.sdf_source is None and sdf_store is None:
+            from .sdf_data import MeshSdfSource, mesh_sdf_enabled, procedural_templates
+            if mesh_sdf_enabled(cfg):       # cfg.sdf_source = "mesh" / HOISDF_SDF=mesh without a source: the model's own MANO layer, procedural objects
+                head = getattr(self.model, "mano_head", None)
+                layer = head.mano_layer if head is not None else self.model.ik_mano_layer
+                self.sdf_source = MeshSdfSource(layer, procedural_templates(), cfg)
         if dataset is None and sdf_store is not None:
             dataset = SyntheticSdfDataset(cfg, sdf_store.n_frames, seed=self.rank)
+        elif dataset is None and self.sdf_source is not None:
+            dataset = SyntheticMeshSdfDataset(cfg, self.sdf_source.n_templates, seed=self.rank)
         ds = dataset if dataset is not None else SyntheticDataset(cfg, seed=self.rank)
         bs = batch_size or cfg.train_batch_size
         sampler = torch.utils.data.distributed.DistributedSampler(ds, self.world, self.rank, shuffle=True) \
@@ -290,6 +321,7 @@ class Trainer:
             rng = np.random.default_rng(_mix_seed(getattr(self, "_epoch_seed", self.base_seed), (1 << 20) + self._image_draws))
             apply_image_pipeline(self._image_pipeline, inputs, targets, meta, rng)
         inputs, targets, meta = (T.to_device(x, dev) for x in (inputs, targets, meta))
+        pts = None
         if self.sdf_store is not None and "sdf_frame" in meta:
             c = self.cfg
             self._sdf_draws += 1
@@ -298,6 +330,12 @@ class Trainer:
                 c.points_filter_dist, c.hand_sdf_scale, c.obj_sdf_scale, train=True,
                 seed=_mix_seed(self._epoch_seed, self._sdf_draws),
                 do_flip=meta.get("do_flip"), rot_mat=meta.get("aug_rot"))
+        elif self.sdf_source is not None and "obj_cls" in meta and "hand_sdf_points" not in inputs:
+            c = self.cfg
+            self._sdf_draws += 1
+            pts = self.sdf_source.make_inputs(targets, meta, c.num_samp_hand, c.num_samp_obj, c.points_filter_dist, c.hand_sdf_scale,
+                                              c.obj_sdf_scale, train=True, seed=_mix_seed(self._epoch_seed, self._sdf_draws))
+        if pts is not None:
             for k in ("hand_sdf_points", "obj_sdf_points", "hand_pre_points", "obj_pre_points"):
                 inputs[k] = pts[k]
             targets["hand_sdf"], targets["obj_sdf"] = pts["hand_sdf"], pts["obj_sdf"]

@@ -2456,3 +2456,120 @@ def encoder_infer(prepared: EncoderPrepared, img, want_aux: bool = True):
     ptrs = (C.c_void_p * len(levels))(*(t.data_ptr() for t in levels))
     call("hoisdf_encoder_infer", C.addressof(d), _p(prepared.blob), _p(x), ptrs, _p(aux), _p(prepared.workspace), prepared.workspace.numel(), _st())
     return PyramidNHWC(levels), aux
+
+
+# ---------------------------------------------------------------------------------------------
+# SDF supervision from meshes (csrc/mesh_sdf.hip, the hoisdf_mesh_* entries).  No gradient: these are labels.
+# ---------------------------------------------------------------------------------------------
+class PreparedMesh:
+    """hoisdf_mesh_prepare on a batch of meshes: verts (B, V, 3); faces (F, 3) shared by the batch or (B, F, 3) per sample, any
+    integer dtype; n_faces (B,) = the rows of each sample that count (None: all F).  Holds tris / area / cdf / box on the device."""
+
+    def __init__(self, verts, faces, n_faces=None):
+        verts = verts.contiguous().float()
+        _chk(verts)
+        if verts.dim() != 3 or verts.shape[2] != 3 or faces.shape[-1] != 3 or faces.dim() not in (2, 3):
+            raise ValueError(f"mesh: verts {tuple(verts.shape)} (B, V, 3), faces {tuple(faces.shape)} (F, 3) or (B, F, 3)")
+        dev = verts.device
+        B, V, F = verts.shape[0], verts.shape[1], faces.shape[-2]
+        if faces.dim() == 3 and faces.shape[0] != B:
+            raise ValueError(f"mesh: {faces.shape[0]} face sets for {B} samples")
+        self.faces = faces.to(dev, torch.int32).contiguous()
+        self.n_faces = None if n_faces is None else torch.as_tensor(n_faces).to(dev, torch.int32).contiguous()
+        if self.n_faces is not None and self.n_faces.shape != (B,):
+            raise ValueError("mesh: one face count per sample")
+        self.B, self.V, self.F, self.verts = B, V, F, verts
+        self.stride = 0 if faces.dim() == 2 else 3 * F
+        self.tris = torch.empty(B, F, 12, device=dev, dtype=torch.float32)
+        self.area = torch.empty(B, F, device=dev, dtype=torch.float32)
+        self.cdf = torch.empty(B, F, device=dev, dtype=torch.float32)
+        self.box = torch.empty(B, 8, device=dev, dtype=torch.float32)
+        call("hoisdf_mesh_prepare", _p(verts), B, V, _p(self.faces), self.stride, _p(self.n_faces), F, _p(self.tris), _p(self.area),
+             _p(self.cdf), _p(self.box), _st())
+
+
+def _as_prepared(verts, faces, n_faces) -> PreparedMesh:
+    return verts if isinstance(verts, PreparedMesh) else PreparedMesh(verts, faces, n_faces)
+
+
+@torch.no_grad()
+def mesh_sdf(points, verts, faces=None, n_faces=None, vert_label=None, out=None, extras: bool = False):
+    """Exact signed distance of points (B, N, >= 3) (xyz first, unit inner stride) to the mesh of their sample; ``verts`` may be a
+    PreparedMesh.  vert_label (V,) shared or (B, V) ints: also the label of the nearest vertex-corner.  ``out`` (B, N) float32 view
+    with any element stride inside a row block (e.g. ``rows[..., 3]``) receives the distances in place.
+    -> sdf (B, N) [, label (B, N) int32]; with extras a dict: sdf, face, bary, winding [, label]."""
+    m = _as_prepared(verts, faces, n_faces)
+    if points.dim() != 3 or points.shape[0] != m.B or points.shape[2] < 3:
+        raise ValueError(f"mesh_sdf: points {tuple(points.shape)} for {m.B} meshes")
+    if points.stride(2) != 1 or points.stride(0) != points.shape[1] * points.stride(1) or points.dtype != torch.float32:
+        points = points.float().contiguous()
+    _chk(points)
+    B, N, dev = m.B, points.shape[1], points.device
+    if out is None:
+        out = torch.empty(B, N, device=dev, dtype=torch.float32)
+    if out.shape != (B, N) or out.dtype != torch.float32 or (N and out.stride(0) != N * out.stride(1)) or out.stride(1) < 1:
+        raise ValueError("mesh_sdf: out must be a (B, N) float32 view whose rows follow each other")
+    _chk(out)
+    lab = stride = None
+    if vert_label is not None:
+        lab = vert_label.to(dev, torch.int32).contiguous()
+        if lab.shape not in ((m.V,), (B, m.V)):
+            raise ValueError(f"mesh_sdf: vert_label {tuple(lab.shape)} for {m.V} vertices")
+        stride = 0 if lab.dim() == 1 else m.V
+    label = torch.empty(B, N, device=dev, dtype=torch.int32) if lab is not None else None
+    face = torch.empty(B, N, device=dev, dtype=torch.int32) if extras else None
+    bary = torch.empty(B, N, 3, device=dev, dtype=torch.float32) if extras else None
+    wind = torch.empty(B, N, device=dev, dtype=torch.float32) if extras else None
+    call("hoisdf_mesh_sdf", _p(points), points.stride(1), B, N, _p(m.tris), _p(m.box), _p(m.n_faces), m.F, _p(lab), stride or 0,
+         _p(out), out.stride(1) if N else 1, _p(face), _p(bary), _p(wind), _p(label), _st())
+    if extras:
+        r = {"sdf": out, "face": face, "bary": bary, "winding": wind}
+        if label is not None:
+            r["label"] = label
+        return r
+    return out if label is None else (out, label)
+
+
+@torch.no_grad()
+def mesh_sample_points(verts, faces=None, n_faces=None, n_points: int = 0, sigma=(0.01, 0.003), uniform_every: int = 16,
+                       pad: float = 0.05, seed: int = 0, with_faces: bool = False):
+    """n_points query points per sample around the mesh (``verts`` may be a PreparedMesh): near-surface with sigma[0] / sigma[1],
+    every ``uniform_every``-th uniform in the box padded by ``pad``; a pure function of (seed, sample, index).
+    -> points (B, n_points, 3) [, face (B, n_points) int32: the face a near-surface point started from, -1 for a box point]"""
+    m = _as_prepared(verts, faces, n_faces)
+    dev = m.tris.device
+    pts = torch.empty(m.B, n_points, 3, device=dev, dtype=torch.float32)
+    face = torch.empty(m.B, n_points, device=dev, dtype=torch.int32) if with_faces else None
+    call("hoisdf_mesh_sample_points", _p(m.tris), _p(m.cdf), _p(m.box), _p(m.n_faces), m.F, m.B, n_points, float(sigma[0]),
+         float(sigma[1]), int(uniform_every), float(pad), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(pts), 3, _p(face), _st())
+    return (pts, face) if with_faces else pts
+
+
+@torch.no_grad()
+def mesh_sdf_rows(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces, hand_vert_label, n_hand: int, n_obj: int,
+                  sigma=(0.01, 0.003), uniform_every: int = 16, pad: float = 0.05, clamp: float = 0.05, seed: int = 0):
+    """hoisdf_mesh_sdf_rows: hand mesh (B, Vh, 3) with shared faces (Fh, 3), object mesh (B, Vo, 3) with faces (B, Fo, 3) (or
+    shared (Fo, 3)) and face counts obj_n_faces (B,) or None -> rows (B, n_hand + n_obj, 6) = [x y z sdf_hand sdf_obj label]."""
+    hand_verts, obj_verts = hand_verts.contiguous().float(), obj_verts.contiguous().float()
+    _chk(hand_verts, obj_verts)
+    dev, B = hand_verts.device, hand_verts.shape[0]
+    if obj_verts.shape[0] != B or hand_verts.dim() != 3 or obj_verts.dim() != 3:
+        raise ValueError("mesh_sdf_rows: one hand and one object mesh per sample")
+    hf = hand_faces.to(dev, torch.int32).contiguous()
+    of = obj_faces.to(dev, torch.int32).contiguous()
+    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
+    lab = hand_vert_label.to(dev, torch.int32).contiguous()
+    if lab.shape != (hand_verts.shape[1],) or hf.dim() != 2 or (of.dim() == 3 and of.shape[0] != B) or (on is not None and on.shape != (B,)):
+        raise ValueError("mesh_sdf_rows: hand faces (Fh, 3), one label per hand vertex, object faces (Fo, 3) or (B, Fo, 3), counts (B,)")
+    Fh, Fo = hf.shape[0], of.shape[-2]
+    mh = _lib.Mesh(verts=hand_verts.data_ptr(), faces=hf.data_ptr(), n_faces=None, face_batch_stride=0, V=hand_verts.shape[1], max_faces=Fh)
+    mo = _lib.Mesh(verts=obj_verts.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
+                   face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=obj_verts.shape[1], max_faces=Fo)
+    nws = lib().hoisdf_mesh_sdf_rows_workspace_bytes(B, Fh, Fo)
+    if nws < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    rows = torch.empty(B, n_hand + n_obj, 6, device=dev, dtype=torch.float32)
+    call("hoisdf_mesh_sdf_rows", C.addressof(mh), C.addressof(mo), _p(lab), B, n_hand, n_obj, float(sigma[0]), float(sigma[1]),
+         int(uniform_every), float(pad), float(clamp), int(seed) & 0x7FFFFFFFFFFFFFFF, _p(rows), 6, _p(ws), nws, _st())
+    return rows

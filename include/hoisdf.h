@@ -1072,6 +1072,70 @@ int hoisdf_image_crop(const hoisdf_frame* frames, const hoisdf_crop* crops, int 
 int hoisdf_image_augment(const hoisdf_frame* frames, const hoisdf_crop* crops, const hoisdf_photo* photo, int B, int res, int hm,
                          int nchw, float* img, uint8_t* crop_u8, uint32_t* lsum, float* hand_seg, float* obj_seg, void* stream);
 
+/* ---- mesh SDF: the rows [x y z sdf_hand sdf_obj label] of sdf_processed/<frame>.npy from the two meshes of a step ------------
+ * reference: tool/pre_process_sdf.py:140-148 only REPACKS such rows; the mesh-to-SDF pass that makes them is an offline CPU tool
+ * outside the reference.  csrc/mesh_sdf.hip; hoisdf_amd/mesh_sdf_oracle.py restates it in numpy.  Lengths are metres in the frame
+ * of the vertices (camera metres for the training path); no gradient; fixed order everywhere: two calls give the same bits.
+ * Every entry checks its arguments before any launch (HOISDF_ERR_INVALID: a required pointer null, a negative count, B > 65535,
+ *   max_faces > HOISDF_MESH_MAX_FACES, a row stride too short) and returns 0 with nothing launched for B = 0 or N = 0.
+ *
+ * hoisdf_mesh_prepare (1 launch): verts [B][V][3]; faces int32 [max_faces][3] shared by the batch (face_batch_stride = 0) or
+ *   [B][...] with face_batch_stride int32 elements (>= 3 max_faces) between samples; n_faces [B] DEVICE int32 (NULL: max_faces
+ *   everywhere; values are clamped to 0 .. max_faces): face rows from n_faces[b] on are padding and are never read.  Faces are
+ *   wound counter-clockwise seen from outside.  Out, per sample: tris [B][max_faces][12] floats (16-byte aligned) = the three
+ *   corners minus the sample's CENTRE, each followed by its vertex index as int32 bits (-1 in the first slot: a skipped face);
+ *   area [B][max_faces]; cdf [B][max_faces] = the inclusive prefix sum of the areas in face order; box [B][8] = centre xyz, total
+ *   area, half extent xyz, 0.  The centre is that of the bounding box of the sample's V vertices: the queries subtract it too, so
+ *   the fp32 arithmetic happens at the size of the mesh, not at its camera depth.
+ *   Skipped-face rule: a face whose normal (b - a) x (c - a), every product rounded on its own, is exactly (0, 0, 0) - two equal
+ *   indices, coincident points - or which names a vertex outside 0 .. V-1 is skipped: area 0 (the sampler never picks it), no
+ *   part in distance or sign.
+ * hoisdf_mesh_sample_points (1 launch): N points per sample into points[(b N + i) ldp + 0..2] (ldp >= 3), stateless: a pure
+ *   function of (seed, b, i).  Kind of point i, from i alone: with k = i mod uniform_every, k = uniform_every - 1 is UNIFORM in
+ *   the box (half extent + pad); otherwise near-surface with sigma1 (k even) or sigma2 (k odd); uniform_every <= 0: no uniform
+ *   points, k = i.  Near-surface: face = the first with cdf > u total (area-weighted), barycentrics (1 - sqrt(u1),
+ *   sqrt(u1) (1 - u2), sqrt(u1) u2), plus isotropic Gaussian noise of that sigma.  A mesh without area gets box points only.
+ *   face_out [B][N] int32 (may be NULL) = the face picked, -1 for a box point.
+ * hoisdf_mesh_sdf (1 launch): points[(b N + i) ldp + 0..2] against the prepared mesh of sample b.  For every face not skipped:
+ *   the exact closest point of the triangle (vertex, edge and face regions) and the solid angle 2 atan2(det[a b c], |a||b||c| +
+ *   (a.b)|c| + (b.c)|a| + (c.a)|b|) of the corners seen from the point.
+ *   Sign rule: winding = sum of the solid angles / 4 pi; sdf = -distance where winding > 0.5, else +distance.  (Not
+ *   pseudonormals: the hand mesh is open at the wrist and templates need not be manifold; the winding number degrades
+ *   gracefully on both.)  Tie rule: faces are visited in ascending order and a face replaces the best only when strictly
+ *   nearer, so the LOWEST face index wins an exact tie; likewise the earliest corner wins equal barycentric weights.
+ *   sdf[(b N + i) ld] (ld >= 1: pass the address of the column - outputs land in a column of a wider row block); optional,
+ *   may be NULL: face_out [B][N] int32 (-1: no usable face; the distance is then 3e38), bary_out [B][N][3] = weights of the
+ *   face's corners at the closest point, winding_out [B][N], label_out [B][N] int32 = vert_label[the corner with the largest
+ *   weight] (vert_label int32 [V], label_batch_stride elements between samples, 0 = shared; required with label_out).
+ * hoisdf_mesh_sdf_rows (6 launches): the composite.  rows [B][n_hand + n_obj][ld] floats, ld >= 6, in the layout of
+ *   tool/pre_process_sdf.py:140-148: per sample n_hand points sampled at the hand mesh, then n_obj sampled at the object mesh
+ *   (seeds 2 seed and 2 seed + 1); on EVERY row column 3 = sdf to the hand, column 4 = sdf to the object; column 5 = the hand
+ *   part hand_vert_label[..] where the row is a hand row and |sdf_hand| <= clamp, else -1 (object rows: always -1); columns from
+ *   6 on are not touched.  The reference applies its clamp in units normalised by its hand scale; here clamp is metres and a
+ *   parameter.  workspace: hoisdf_mesh_sdf_rows_workspace_bytes(B, hand max_faces, obj max_faces) device bytes (-1 on an
+ *   invalid shape), 256-byte aligned. */
+#define HOISDF_MESH_MAX_FACES 4096
+#define HOISDF_MESH_TILE 128
+typedef struct {
+  const float* verts;
+  const int32_t* faces;
+  const int32_t* n_faces;
+  long face_batch_stride;
+  int V, max_faces;
+} hoisdf_mesh;
+int hoisdf_mesh_prepare(const float* verts, int B, int V, const int32_t* faces, long face_batch_stride, const int32_t* n_faces,
+                        int max_faces, float* tris, float* area, float* cdf, float* box, void* stream);
+int hoisdf_mesh_sample_points(const float* tris, const float* cdf, const float* box, const int32_t* n_faces, int max_faces, int B,
+                              int N, float sigma1, float sigma2, int uniform_every, float pad, uint64_t seed, float* points,
+                              int ldp, int32_t* face_out, void* stream);
+int hoisdf_mesh_sdf(const float* points, int ldp, int B, int N, const float* tris, const float* box, const int32_t* n_faces,
+                    int max_faces, const int32_t* vert_label, long label_batch_stride, float* sdf, int ld, int32_t* face_out,
+                    float* bary_out, float* winding_out, int32_t* label_out, void* stream);
+long hoisdf_mesh_sdf_rows_workspace_bytes(int B, int hand_max_faces, int obj_max_faces);
+int hoisdf_mesh_sdf_rows(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* hand_vert_label, int B, int n_hand,
+                         int n_obj, float sigma1, float sigma2, int uniform_every, float pad, float clamp, uint64_t seed,
+                         float* rows, int ld, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
