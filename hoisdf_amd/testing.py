@@ -445,3 +445,270 @@ def check_mask_statistics(keep_mask, kv_len: int, p: float, sigmas: float = 5.0)
     for name, (f, prob, n, z) in out.items():
         assert abs(z) <= sigmas, f"mask statistics: {name}: frequency {f:.5f} over {n} is {z:+.1f} sigma from {prob:.5f}"
     return out
+
+
+# ---- the small hot-path kernels held to fp64: one plain-torch function per operation ------------------------------------------------
+# Every function takes the float32 CPU inputs the kernel gets, evaluates in ``dtype`` (float64 = the truth; float32 = the same formula
+# at the kernel's precision, the yardstick of the slice-wise bar below) and returns a dict of ``dtype`` tensors; gradients come from
+# autograd and are present when the matching upstream gradient is given.  Nothing here knows how a kernel orders its sums.
+TOKEN_BETA_MIN = float(np.float32(2e-3))       # main/model.py:123-126 clamps the gate's beta here; the float32 constant the kernels hold
+
+
+def _leaf(t: torch.Tensor, dtype) -> torch.Tensor:
+    return t.detach().to(dtype).clone().requires_grad_(True)
+
+
+def reference_posenc_rows(pts, ld: int = 30, col0: int = 0, fill: float = 0.0, dtype=torch.float64) -> torch.Tensor:
+    """(n, ld) buffer as hoisdf_posenc_fwd leaves a ``fill``-filled x0: columns [col0, col0 + 30) = [sin(2^k p), cos(2^k p)], k = 0..4
+    (three coordinates each), [col0 + 30, col0 + 33) = p, [col0 + 33, min(col0 + 36, ld)) = 0, every other element ``fill``.
+    ld = 30, col0 = 0 is the ``pe`` output."""
+    p = pts.detach().reshape(-1, 3).to(dtype)
+    cols = []
+    for k in range(5):
+        cols += [torch.sin(p * float(2 ** k)), torch.cos(p * float(2 ** k))]
+    body = torch.cat(cols + [p, torch.zeros_like(p)], 1)                      # 36 columns
+    out = torch.full((p.shape[0], ld), fill, dtype=dtype)
+    n = min(36, ld - col0)
+    out[:, col0:col0 + n] = body[:, :n]
+    return out
+
+
+def reference_weight_norm(v, g, dW=None, ldw=None, dtype=torch.float64):
+    """W [out, ldw] = g * v / ||v||_row in columns [0, in), 0 in the pad; norms [out]; dv, dg for dW [out, ldw] (its pad is not read)"""
+    out_, in_ = v.shape
+    ldw = in_ if ldw is None else ldw
+    v_, g_ = _leaf(v, dtype), _leaf(g.reshape(out_), dtype)
+    norms = v_.pow(2).sum(1).sqrt()
+    W = torch.cat([v_ * (g_ / norms)[:, None], torch.zeros(out_, ldw - in_, dtype=dtype)], 1)
+    res = dict(W=W.detach(), norms=norms.detach())
+    if dW is not None:
+        W.backward(dW.detach().to(dtype))
+        res.update(dv=v_.grad, dg=g_.grad)
+    return res
+
+
+def reference_sdf_head(h, w, b, clamp: float, dsdf=None, dtype=torch.float64):
+    """pre = h w + b, raw = tanh(pre), sdf = clamp(raw, +-clamp) (torch.clamp: the gradient passes on |raw| <= clamp);
+    dh [M, K], dw [K], db [1] for dsdf [M]"""
+    h_, w_, b_ = _leaf(h, dtype), _leaf(w.reshape(-1), dtype), _leaf(b.reshape(1), dtype)
+    pre = h_ @ w_ + b_
+    raw = torch.tanh(pre)
+    sdf = raw.clamp(-clamp, clamp)
+    res = dict(pre=pre.detach(), raw=raw.detach(), sdf=sdf.detach())
+    if dsdf is not None:
+        sdf.backward(dsdf.detach().reshape(-1).to(dtype))
+        res.update(dh=h_.grad, dw=w_.grad, db=b_.grad)
+    return res
+
+
+def reference_token_build(cam, center, pe, feat, sdf, beta, dtok=None, dtype=torch.float64):
+    """tok [B, P, D] = [cam - center | pe | feat * sigmoid(sdf / beta_eff) / beta_eff], beta_eff = max(beta, 2e-3) as the reference
+    model clamps it; dfeat [B, P, D - 33] and dbeta [1] - the gradient with respect to beta_eff - for dtok [B, P, D].
+    cam (B, P, 3), center (B, 3), pe (B, P, 30), feat (B, P, D - 33), sdf (B, P)"""
+    B, P = sdf.shape[0], sdf.shape[1]
+    feat_ = _leaf(feat.reshape(B, P, -1), dtype)
+    beta_eff = _leaf(torch.clamp(beta.detach().reshape(1).float(), min=TOKEN_BETA_MIN), dtype)
+    sig = torch.sigmoid(sdf.detach().reshape(B, P, 1).to(dtype) / beta_eff) / beta_eff
+    tok = torch.cat([cam.detach().reshape(B, P, 3).to(dtype) - center.detach().to(dtype)[:, None],
+                     pe.detach().reshape(B, P, 30).to(dtype), feat_ * sig], 2)
+    res = dict(tok=tok.detach(), beta_eff=beta_eff.detach())
+    if dtok is not None:
+        tok.backward(dtok.detach().to(dtype))
+        res.update(dfeat=feat_.grad, dbeta=beta_eff.grad)
+    return res
+
+
+def reference_vote(off, cls, pts, dj=None, dtype=torch.float64):
+    """joints [L, B, J, 3] = sum_p softmax_p(cls)[p] (pts[p] + off[p, j]); doff, dcls for dj.  off (L, B, P, J * 3), cls (L, B, P, J),
+    pts (B, P, 3); any J"""
+    L, B, P, J = cls.shape
+    off_, cls_ = _leaf(off, dtype), _leaf(cls, dtype)
+    vote = pts.detach().to(dtype)[None, :, :, None, :] + off_.view(L, B, P, J, 3)
+    joints = (vote * torch.softmax(cls_, dim=2).unsqueeze(-1)).sum(2)
+    res = dict(joints=joints.detach())
+    if dj is not None:
+        joints.backward(dj.detach().to(dtype))
+        res.update(doff=off_.grad, dcls=cls_.grad)
+    return res
+
+
+def vote_near(pts, gt_mm, radius: float):
+    """float64 distances ||p - gt / 1000|| (B, P, J) and the mask distance < radius, from the float32 inputs"""
+    d = (pts.detach().double()[:, :, None, :] - gt_mm.detach().double()[:, None] / 1000.0).norm(dim=-1)
+    return d, d < radius
+
+
+def reference_vote_loss(off, cls, pts, gt_mm, radius: float, dj=None, dl3d=None, dbce=None, dtype=torch.float64):
+    """reference_vote plus the JointvoteLoss sums (common/nets/loss.py:31-56) with near = ||p - gt / 1000|| < radius (always decided
+    in float64): l3d_sum [L, B] = sum_{p, j, xyz} smooth_l1(1000 vote - gt) near, bce_sum [L, B] = sum_{p, j} bce_with_logits(cls,
+    near), near_sum [B] = sum_{p, j} near.  doff, dcls for whichever of dj [L, B, J, 3], dl3d [L, B], dbce [L, B] are given."""
+    L, B, P, J = cls.shape
+    off_, cls_ = _leaf(off, dtype), _leaf(cls, dtype)
+    gt = gt_mm.detach().to(dtype)
+    near = vote_near(pts, gt_mm, radius)[1].to(dtype)                                      # (B, P, J)
+    vote = pts.detach().to(dtype)[None, :, :, None, :] + off_.view(L, B, P, J, 3)
+    joints = (vote * torch.softmax(cls_, dim=2).unsqueeze(-1)).sum(2)
+    x = vote * 1000.0 - gt[None, :, None]
+    sl1 = torch.where(x.abs() < 1.0, 0.5 * x * x, x.abs() - 0.5)
+    l3d = (sl1 * near[None, ..., None]).sum((2, 3, 4))
+    bce = (cls_.clamp(min=0) - cls_ * near[None] + torch.log1p(torch.exp(-cls_.abs()))).sum((2, 3))
+    res = dict(joints=joints.detach(), l3d_sum=l3d.detach(), bce_sum=bce.detach(), near_sum=near.sum((1, 2)))
+    if dj is not None or dl3d is not None or dbce is not None:
+        total = sum((o * g.detach().to(dtype)).sum() for o, g in ((joints, dj), (l3d, dl3d), (bce, dbce)) if g is not None)
+        total.backward()
+        res.update(doff=off_.grad, dcls=cls_.grad)
+    return res
+
+
+def reference_add_layernorm(x, r, keep_mask, p: float, gamma, beta, eps: float = 1e-5, dy=None, dtype=torch.float64):
+    """y = LN(x + r * keep_mask / (1 - p)) over the last dimension (biased variance), r / keep_mask None = plain LayerNorm;
+    dx, dr (None without r), dgamma, dbeta for dy"""
+    x_, g_, b_ = _leaf(x, dtype), _leaf(gamma, dtype), _leaf(beta, dtype)
+    r_ = None if r is None else _leaf(r, dtype)
+    a = x_
+    if r_ is not None:
+        a = x_ + (r_ if keep_mask is None else r_ * keep_mask.to(dtype) / (1.0 - p))
+    mu = a.mean(-1, keepdim=True)
+    var = (a - mu).pow(2).mean(-1, keepdim=True)
+    y = (a - mu) * torch.rsqrt(var + eps) * g_ + b_
+    res = dict(y=y.detach())
+    if dy is not None:
+        y.backward(dy.detach().to(dtype))
+        res.update(dx=x_.grad, dr=None if r_ is None else r_.grad, dgamma=g_.grad, dbeta=b_.grad)
+    return res
+
+
+# ---- bars: the tensor-wide measure of tests/test_gpu_ops.py and a slice-wise one for tensors whose slices span decades ---------------
+def rel_err(got, ref) -> float:
+    """largest |got - ref| over the largest |ref| of the whole tensor"""
+    return _rel_err(got, ref)
+
+
+def slice_err(got, ref, slice_dims: int) -> float:
+    """the largest, over slices, of (largest |got - ref| of the slice) / (largest |ref| of the slice).  A slice is one index of the
+    first ``slice_dims`` dimensions (dcls (L, B, P, J) moved to (L, B, J, P) has slice_dims = 3: one slice per (l, b, j))."""
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    n = math.prod(ref.shape[:slice_dims])
+    g, f = got.reshape(n, -1), ref.reshape(n, -1)
+    return float(((g - f).abs().amax(1) / f.abs().amax(1).clamp(min=1e-30)).max())
+
+
+def slice_bar(ref32, ref64, slice_dims: int, tensor_bar: float) -> Tuple[float, float]:
+    """(bar, fp32 error): the slice-wise bar is the larger of the tensor-wide bar and four times the slice-wise error of the SAME formula
+    evaluated in float32 on the CPU (ref32) against float64 - a measurement that does not involve the kernel; four allows for another
+    summation order"""
+    e32 = slice_err(ref32, ref64, slice_dims)
+    return max(tensor_bar, 4.0 * e32), e32
+
+
+# ---- conditions on the inputs: two comparisons flip on a last bit, so no input may sit on their threshold ---------------------------
+def vote_points_margin(pts, gt_mm, radius: float) -> float:
+    """smallest | ||p - gt / 1000|| - radius | over every (b, p, j), in float64"""
+    return float((vote_near(pts, gt_mm, radius)[0] - radius).abs().min())
+
+
+def condition_vote_points(pts, gt_mm, radius: float, draw, seed: int, margin: float = 1e-6, max_rounds: int = 64):
+    """Re-draws (``draw(generator, n) -> (n, 3)`` float32, from a second stream seeded ``seed``) every point of pts (B, P, 3) that has
+    any joint with | ||p - gt / 1000|| - radius | < margin, until none is left.  -> (points, number of re-drawn points)"""
+    pts = pts.detach().clone()
+    g = torch.Generator().manual_seed(seed)
+    redrawn = 0
+    for _ in range(max_rounds):
+        bad = ((vote_near(pts, gt_mm, radius)[0] - radius).abs() < margin).any(-1)         # (B, P)
+        n = int(bad.sum())
+        if n == 0:
+            return pts, redrawn
+        pts[bad] = draw(g, n).to(pts.dtype)
+        redrawn += n
+    raise RuntimeError(f"condition_vote_points: points within {margin} of the radius after {max_rounds} rounds")
+
+
+def head_rows_margin(h, w, b, clamp: float) -> float:
+    """smallest | |tanh(h w + b)| - clamp | over the rows, in float64"""
+    return float((reference_sdf_head(h, w, b, clamp)["raw"].abs() - clamp).abs().min())
+
+
+def condition_head_rows(h, w, b, clamp: float, draw, seed: int, margin: float = 1e-5, max_rounds: int = 64):
+    """Re-draws (``draw(generator, n) -> (n, K)`` float32) every row of h (M, K) with | |tanh(h w + b)| - clamp | < margin in float64,
+    until none is left.  -> (h, number of re-drawn rows)"""
+    h = h.detach().clone()
+    g = torch.Generator().manual_seed(seed)
+    redrawn = 0
+    for _ in range(max_rounds):
+        bad = (reference_sdf_head(h, w, b, clamp)["raw"].abs() - clamp).abs() < margin
+        n = int(bad.sum())
+        if n == 0:
+            return h, redrawn
+        h[bad] = draw(g, n).to(h.dtype)
+        redrawn += n
+    raise RuntimeError(f"condition_head_rows: rows within {margin} of the clamp after {max_rounds} rounds")
+
+
+# ---- the seeded inputs of tests/test_gpu_small_kernels.py for the two conditioned operations (tests/test_small_kernel_refs.py shows,
+# without a GPU, that the conditioners end and hold at every one of these shapes)
+HEAD_CLAMP = 0.15
+HEAD_KS = (4, 256, 260, 512, 1024)             # the forward's; the backward serves K <= 512
+HEAD_MS = (1, 5, 4097, 9001)
+VOTE_RADIUS = 0.04
+VOTE_JS = (1, 20, 21, 64)
+VOTE_LBPS = ((1, 1, 1), (3, 2, 5), (3, 2, 257), (1, 1, 1025))
+VOTE_CASES = tuple((L, B, P, J) for (L, B, P) in VOTE_LBPS for J in VOTE_JS) + ((6, 86, 520, 4),)
+VOTE_FAMILIES = ("randn", "equal", "spike")
+VOTE_POINTS_SALT = 2            # (the stream of the point draws; the conditioner makes any stream fit)
+
+
+def _gen(*key) -> torch.Generator:
+    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
+
+
+def head_saturated_rows(M: int):
+    """rows of a head case put at pre-activation -+20: two of a handful of rows, four of many"""
+    return sorted({r for r in ((1, M - 1) if M < 100 else (1, 3, M // 2, M - 1)) if 0 < r < M})
+
+
+def head_case_inputs(M: int, K: int):
+    """h (M, K), w (K), b (1), dsdf (M) of one SDF-head case, conditioned: pre-activations ~ N(-0.02, 0.156^2) - about a third of the
+    rows beyond the 0.15 clamp - head_saturated_rows(M) at pre-activation -+20, where tanh is exactly -+1 in float32 and float64;
+    no row within 1e-5 of the clamp.  -> (h, w, b, dsdf, rows re-drawn)"""
+    g = _gen("head", M, K)
+    h = torch.randn(M, K, generator=g)
+    w = torch.randn(K, generator=g)
+    w = w * (0.156 / float(w.norm()))
+    b = torch.tensor([-0.02])
+    dsdf = torch.randn(M, generator=g)
+    for n, r in enumerate(head_saturated_rows(M)):
+        h[r] = w * ((-20.0 if n % 2 else 20.0) / float(w.double().pow(2).sum()))
+    h, redrawn = condition_head_rows(h, w, b, HEAD_CLAMP, lambda gg, n: torch.randn(n, K, generator=gg), zlib.crc32(b"head2") + M + K)
+    return h, w, b, dsdf, redrawn
+
+
+def vote_case_points(B: int, P: int, J: int, far_sample=None, salt=None):
+    """pts (B, P, 3) ~ N(0, 0.05^2) m and gt (B, J, 3) mm = a point of the sample + N(0, 15^2) mm (so some points lie inside the 40 mm
+    radius), ``far_sample``'s joints moved a metre away (none of its points is near); UNCONDITIONED -> (pts, gt, draw)"""
+    g = _gen("vote-points", VOTE_POINTS_SALT if salt is None else salt, B, P, J)
+    pts = torch.randn(B, P, 3, generator=g) * 0.05
+    gt = pts[:, torch.arange(J) % P] * 1000.0 + torch.randn(B, J, 3, generator=g) * 15.0
+    if far_sample is not None:
+        gt[far_sample] += 1000.0
+    return pts, gt, (lambda gg, n: torch.randn(n, 3, generator=gg) * 0.05)
+
+
+def vote_case_inputs(L: int, B: int, P: int, J: int, family: str, far_sample=None, salt=None):
+    """conditioned pts, gt and off (L, B, P, J * 3), cls (L, B, P, J) of the logit ``family``: "randn"; "equal" (every logit 0.75);
+    "spike" (randn * 30 - 1e4 with one point per (l, b, j) at +100: exp(100) overflows float32, so a softmax that does not subtract the
+    maximum gives Inf / NaN).  -> (off, cls, pts, gt, points re-drawn)"""
+    pts, gt, draw = vote_case_points(B, P, J, far_sample, salt)
+    pts, redrawn = condition_vote_points(pts, gt, VOTE_RADIUS, draw, zlib.crc32(b"vote2") + P + J)
+    g = _gen("vote", L, B, P, J, family)
+    off = torch.randn(L, B, P, J * 3, generator=g) * 0.02
+    if family == "randn":
+        cls = torch.randn(L, B, P, J, generator=g)
+    elif family == "equal":
+        cls = torch.full((L, B, P, J), 0.75)
+    elif family == "spike":
+        cls = torch.randn(L, B, P, J, generator=g) * 30.0 - 1e4
+        cls.scatter_(2, torch.randint(0, P, (L, B, 1, J), generator=g), 100.0)
+    else:
+        raise ValueError(family)
+    return off, cls, pts, gt, redrawn

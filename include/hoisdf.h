@@ -306,10 +306,13 @@ int hoisdf_lattice_fill(const float* center, const float* cam_intr, const float*
                         int32_t* sample_idx, int32_t* lattice_idx, void* stream);
 /* Per sample b, select the k rows with the smallest |sdf_raw| among rows
  * [offsets[b], offsets[b]+counts[b]) (ties: lower row first) and emit them in ascending
- * (|sdf|, row) order: sel [B][k] int32 global row indices.  Exact (radix select + rank). */
+ * (|sdf|, row) order: sel [B][k] int32 global row indices.  Exact (radix select + rank).
+ * Keys compare by the bit pattern of |x|: +0 and -0 tie, Inf sorts after every finite value and NaN after Inf.
+ * The caller checks counts[b] >= k.  A sample with counts[b] < k is not an error here: its k entries of sel are all -1 and
+ * the other samples are unaffected; hoisdf_gather_rows writes a row of zeros for an index of -1. */
 int hoisdf_select_smallest_abs(const float* sdf_raw, const int32_t* offsets, const int32_t* counts,
                                int B, int k, int32_t* sel, void* stream);
-/* out[r][0:width] = src[sel[r]][0:width] */
+/* out[r][0:width] = src[sel[r]][0:width]; sel[r] < 0: out[r][0:width] = 0 */
 int hoisdf_gather_rows(const float* src, int lds, const int32_t* sel, long n_sel, int width,
                        float* out, int ldo, void* stream);
 /* ---- the training-time SDF query, one call per direction (SURVEY.md section 8(b) `hoisdf_sdf_query_bwd`) ------------------
