@@ -67,6 +67,13 @@ class Config:
     mesh_sdf_pad = 0.05                  # metres around the mesh's bounding box
     mesh_sdf_candidates = 4              # candidate rows per sample = this x num_samp_hand (num_samp_obj)
     mesh_sdf_label_clamp = 0.05          # metres: a hand row keeps its part label where |sdf_hand| <= this
+    # not in the reference: test.py's Evaluator also reports whether the PREDICTED hand and the PREDICTED object are physically
+    # compatible - penetration depth, contact ratio, intersection volume (hoisdf_eval_interaction, csrc/interact.hip) - in a block
+    # appended to results.txt.  Also HOISDF_INTERACTION=1 / test.py --interaction.  5 mm voxels are ObMan's; 5 mm contact is a
+    # definition, not a measurement
+    eval_interaction = False
+    contact_dist = 0.005                 # metres: a hand vertex this close to the object (or inside it) is in contact
+    interaction_voxel = 0.005            # metres: the cell of the intersection-volume grid (at most 64 cells per axis)
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

@@ -19,33 +19,11 @@
 // The four partial answers of a point meet in LDS and wave 0 combines them in wave order: strictly nearer wins, the LOWER face
 // index on an exact tie - so the nearest face is the lowest index among equals whatever the tile and wave order - and the angle
 // sums are added in one fixed order.
-#include "common.h"
+// The vector helpers, atan2_poly, MeshSdfArgs, the workspace carving and the declarations of the two launches that interact.hip
+// runs as well are in mesh.h.
+#include "mesh.h"
 
 namespace hoisdf {
-
-constexpr int MESH_TILE = 128;            // faces per LDS tile: 6 KiB, 384 float4 = 1.5 loads per thread of a 256-thread block
-static_assert(HOISDF_MESH_TILE == MESH_TILE, "the header states the tile the tests aim at");
-
-struct f3 { float x, y, z; };
-__device__ __forceinline__ f3 sub(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ f3 xyz(const float4& v) { return {v.x, v.y, v.z}; }
-
-// u x v with every product rounded on its own: u x u and 0 x v are then EXACTLY zero (a fused multiply-add would leave the
-// rounding error of one product behind), which is what the skipped-face rule tests
-__device__ __forceinline__ f3 cross_unfused(f3 u, f3 v) {
-#pragma clang fp contract(off)
-  f3 n;
-  n.x = u.y * v.z - u.z * v.y;
-  n.y = u.z * v.x - u.x * v.z;
-  n.z = u.x * v.y - u.y * v.x;
-  return n;
-}
-
-__device__ __forceinline__ int sample_faces(const int32_t* n_faces, int b, int max_faces) {
-  const int n = n_faces ? n_faces[b] : max_faces;
-  return n < 0 ? 0 : (n > max_faces ? max_faces : n);
-}
 
 // ---- a. triangle preparation -----------------------------------------------------------------------------------------------------
 // tris [B][max_faces][3] float4: (a, b, c) - centre, .w = the bits of the three vertex indices; a.w = -1 marks a skipped face.
@@ -194,41 +172,6 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float4* __restri
 }
 
 // ---- c. signed distance ----------------------------------------------------------------------------------------------------------
-struct MeshSdfArgs {
-  const float* points; int ldp;          // [B][N] rows of ldp floats, xyz first
-  const float4* tris; const float* box; const int32_t* n_faces; int max_faces;
-  int N;
-  float* sdf; int ld;                    // sdf of point (b, i) -> sdf[(b N + i) ld]  (the caller folds the column into the pointer)
-  int32_t* face_out;                     // [B][N] or null
-  float* bary_out;                       // [B][N][3] or null
-  float* winding_out;                    // [B][N] or null
-  const int32_t* vert_label; long label_stride;   // [V] per sample (stride 0: shared) or null
-  int32_t* label_out;                    // [B][N] or null
-  float* label_f; float clamp; int n_label;       // rows form: label as a float at label_f[(b N + i) ld]: the vertex label where
-                                                  // i < n_label and |sdf| <= clamp, else -1; null: not wanted
-};
-
-// atan2(y, x) to 1.1e-7 rad: one hardware reciprocal and a degree-17 odd polynomial on [0, 1] (the library routine costs about three
-// times as much, and the sign rule compares a sum of <= 4096 of these, each at most pi, with 0.5 of 2 pi); 0 for y = x = 0
-__device__ __forceinline__ float atan2_poly(float y, float x) {
-  const float ax = fabsf(x), ay = fabsf(y), mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-  const float t = mx > 0.f ? mn * __builtin_amdgcn_rcpf(mx) : 0.f, s = t * t;
-  float r = 0.00282363896f;
-  r = r * s - 0.0159569028f;
-  r = r * s + 0.0425049886f;
-  r = r * s - 0.0748900920f;
-  r = r * s + 0.106347933f;
-  r = r * s - 0.142027363f;
-  r = r * s + 0.199926957f;
-  r = r * s - 0.333331018f;
-  r = r * s * t + t;
-  if (ay > ax) r = 1.57079637f - r;
-  if (x < 0.f) r = 3.14159274f - r;
-  return copysignf(r, y);
-}
-
-constexpr int MESH_PTS = 64, MESH_SLICES = 4;          // a block: 64 points (one per lane) x 4 waves, each wave a quarter of the faces
-
 __global__ __launch_bounds__(256) void mesh_sdf_kernel(const MeshSdfArgs a) {
   __shared__ float4 s_tri[MESH_TILE * 3];
   __shared__ float s_best[256], s_v[256], s_w[256], s_om[256];
@@ -317,21 +260,7 @@ __global__ __launch_bounds__(256) void mesh_sdf_kernel(const MeshSdfArgs a) {
 }
 
 // ---- launches --------------------------------------------------------------------------------------------------------------------
-struct MeshBuffers { float4* tris; float* area; float* cdf; float* box; };
-static inline long align256(long n) { return (n + 255) / 256 * 256; }
-static long mesh_buffers_bytes(long B, long max_faces) {
-  return align256(B * max_faces * 48) + 2 * align256(B * max_faces * 4) + align256(B * 32);
-}
-static MeshBuffers carve(char* base, long B, long max_faces) {
-  MeshBuffers m;
-  m.tris = (float4*)base; base += align256(B * max_faces * 48);
-  m.area = (float*)base; base += align256(B * max_faces * 4);
-  m.cdf = (float*)base; base += align256(B * max_faces * 4);
-  m.box = (float*)base;
-  return m;
-}
-
-static bool mesh_shape_ok(const char* what, int B, int V, int max_faces) {
+bool mesh_shape_ok(const char* what, int B, int V, int max_faces) {
   if (B < 0 || B > 65535 || V < 0 || max_faces < 0 || max_faces > HOISDF_MESH_MAX_FACES) {
     set_error("%s: B=%d (0 .. 65535) V=%d max_faces=%d (0 .. %d)", what, B, V, max_faces, HOISDF_MESH_MAX_FACES);
     return false;
@@ -339,8 +268,8 @@ static bool mesh_shape_ok(const char* what, int B, int V, int max_faces) {
   return true;
 }
 
-static void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long face_stride, const int32_t* n_faces,
-                           int max_faces, const MeshBuffers& m, hipStream_t st) {
+void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long face_stride, const int32_t* n_faces, int max_faces,
+                    const MeshBuffers& m, hipStream_t st) {
   hipLaunchKernelGGL(mesh_prepare_kernel, dim3(B), dim3(256), 0, st, verts, V, faces, face_stride, n_faces, max_faces, m.tris, m.area,
                      m.cdf, m.box);
 }
@@ -349,7 +278,7 @@ static void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_
   hipLaunchKernelGGL(mesh_sample_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, st, m.tris, m.cdf, m.box, n_faces, max_faces, N, s1, s2,
                      every, pad, seed, points, pstride, ldp, face_out);
 }
-static void launch_sdf(const MeshSdfArgs& a, int B, hipStream_t st) {
+void launch_sdf(const MeshSdfArgs& a, int B, hipStream_t st) {
   hipLaunchKernelGGL(mesh_sdf_kernel, dim3(cdiv(a.N, MESH_PTS), B), dim3(256), 0, st, a);
 }
 

@@ -15,6 +15,11 @@ The ``*_native`` functions and ``MeshEvalNative`` are the same metrics through t
 ops.eval_*): no distance matrix, an fp64 Jacobi SVD in the kernel, integer threshold counts, running mesh sums on the device.
 Opt-in (``cfg.native_metrics`` / ``HOISDF_METRICS=native`` / ``test.py --native-metrics``); GPU only, no fallback.  ``Evaluator`` is
 the per-batch bookkeeping of test.py over either backend.
+
+Not in the reference: ``Evaluator(interaction=True)`` (``cfg.eval_interaction`` / ``HOISDF_INTERACTION=1`` / ``test.py --interaction``)
+also asks whether the PREDICTED hand and the PREDICTED object are compatible with each other - penetration depth, contact ratio and
+intersection volume, the numbers of ObMan and its successors - through hoisdf_eval_interaction (csrc/interact.hip, ops.eval_interaction)
+and appends them to results.txt.  Off by default: the file is then what the reference writes.
 """
 from __future__ import annotations
 
@@ -195,6 +200,11 @@ def fscore_native(gt: torch.Tensor, pr: torch.Tensor, th: float) -> torch.Tensor
     return ops.eval_mesh(pr, gt, [float(th)])[2][:, 0]
 
 
+def interaction_enabled(cfg=None) -> bool:
+    """cfg.eval_interaction (default False) or HOISDF_INTERACTION=1: the Evaluator appends the interaction block"""
+    return bool(getattr(cfg, "eval_interaction", False)) or os.environ.get("HOISDF_INTERACTION", "") == "1"
+
+
 class MeshEvalNative:
     """``MeshEval`` on the device (hoisdf_eval_accum_*): one fp64 sum per vertex and one count per (threshold, vertex) instead of
     every distance of the test set on the host.  The thresholds are fixed when the object is made, since the counts are taken as
@@ -244,11 +254,31 @@ class Evaluator:
     templates (T,V,3) on the evaluation device; obj_cls (B,) = the template of each sample.  ``native=False`` is the batched torch
     path (every ``feed`` reads its batch means back); ``native=True`` runs the hoisdf_eval_* entries, keeps the running sums, the
     F-scores and the mesh accumulators on the device and reads them once in ``write``.  Only the native path knows samples that are not
-    evaluated (obj_cls < 0): they count for the hand keys and not for the object keys (*_error)."""
+    evaluated (obj_cls < 0): they count for the hand keys and not for the object keys (*_error).
+    ``interaction=True`` (or cfg.eval_interaction / HOISDF_INTERACTION=1; either backend - there is one implementation): every
+    ``feed`` also poses the PREDICTED pair in the camera frame - hand = the predicted MANO mesh + mano_root, object = the template
+    turned and moved by the mean predicted rotation and translation + obj_center_cam - runs ops.eval_interaction on it (cfg.contact_dist,
+    cfg.interaction_voxel) and keeps running sums on the device; ``write`` appends one block after everything else.  It needs the
+    templates as meshes: ``template_faces`` = the ``faces`` (T,F,3) / ``n_faces`` (T,) of sdf_data.pack_templates (whose ``verts`` are
+    ``templates``), and ``hand_faces`` (Fh,3) = the MANO layer's ``th_faces``.  Samples with obj_cls < 0 are not evaluated."""
 
-    def __init__(self, cfg, templates: torch.Tensor, native: bool = False):
+    def __init__(self, cfg, templates: torch.Tensor, native: bool = False, interaction: bool = False,
+                 template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None):
         self.cfg, self.templates, self.native = cfg, templates, bool(native)
         self.dev = templates.device
+        self.interaction = bool(interaction) or interaction_enabled(cfg)
+        if self.interaction:
+            if template_faces is None or hand_faces is None or "faces" not in template_faces:
+                raise ValueError("Evaluator(interaction=True) needs template_faces (faces, n_faces of sdf_data.pack_templates) and hand_faces")
+            self._tfaces = torch.as_tensor(template_faces["faces"]).to(self.dev, torch.int32)
+            n = template_faces.get("n_faces")
+            self._tn = torch.full((self._tfaces.shape[0],), self._tfaces.shape[1], dtype=torch.int32) if n is None else torch.as_tensor(n)
+            self._tn = self._tn.to(self.dev, torch.int32)
+            self._hfaces = torch.as_tensor(hand_faces).to(self.dev, torch.int32)
+            if self._tfaces.dim() != 3 or self._tfaces.shape[0] != templates.shape[0] or self._tn.shape != (templates.shape[0],):
+                raise ValueError(f"template_faces {tuple(self._tfaces.shape)} for {templates.shape[0]} templates")
+            # the sums of max(pen_hand, pen_obj) [m], in_contact, volume [m^3], contact_verts over the evaluated samples, their number
+            self._iacc = torch.zeros(5, device=self.dev, dtype=torch.float64)
         self.ho3d = cfg.dataset == "ho3d"
         keys = ["ADDS_error"] + (["MME_error"] if self.ho3d else ["mano_mje", "mano_pamje", "OCE_error", "MCE_error"])
         self.results = {k: 0.0 for k in keys}                 # torch path: running sums on the host, in cm
@@ -288,6 +318,8 @@ class Evaluator:
             om = obj_metrics(out["obj_rot_out"], out["obj_trans_out"], tg["obj_rot"], tg["rel_obj_trans"],
                              self.templates[obj_cls], ho3d)
         self.total += B
+        if self.interaction:
+            self._feed_interaction(out, meta, obj_cls)
         if ho3d:                                                                  # main/test.py:133-176
             if cfg.use_inverse_kinematics:
                 joints, mesh = out["ik_joints_out"], out["ik_verts_out"]
@@ -326,6 +358,26 @@ class Evaluator:
                 self.f_score.append(torch.stack([fscore(gv, pv, t) for t in self.f_threshs], 1).cpu().numpy())
                 self.f_score_al.append(torch.stack([fscore(gv, al, t) for t in self.f_threshs], 1).cpu().numpy())
 
+    def interaction_per_sample(self, out, meta, obj_cls):
+        """ops.eval_interaction on the predicted pair of every sample -> (its dict, used (B,) bool: obj_cls >= 0)"""
+        from . import ops
+        dev = self.dev
+        root = meta["mano_root"].to(dev)
+        hand = (out["ik_verts_out"] if self.cfg.use_inverse_kinematics else out["mano_mesh_out"]).detach() + root[:, None]
+        cls = torch.as_tensor(obj_cls).to(dev).long()
+        used = cls >= 0
+        cls = cls.clamp_min(0)
+        rot, trans = out["obj_rot_out"].detach().mean(1), out["obj_trans_out"].detach().mean(1)
+        obj = self.templates[cls] @ batch_rodrigues(rot).transpose(1, 2) + (trans + meta["obj_center_cam"].to(dev))[:, None]
+        return ops.eval_interaction(hand, self._hfaces, obj, self._tfaces[cls], self._tn[cls], None, self.cfg.contact_dist,
+                                    self.cfg.interaction_voxel), used
+
+    def _feed_interaction(self, out, meta, obj_cls) -> None:
+        r, used = self.interaction_per_sample(out, meta, obj_cls)
+        vals = torch.stack([torch.maximum(r["pen_hand"], r["pen_obj"]).double(), r["in_contact"].double(), r["volume"].double(),
+                            r["contact_verts"].double(), torch.ones_like(r["volume"]).double()])
+        self._iacc += (vals * used.double()[None]).sum(1)
+
     def write(self, out_dir: str) -> str:
         """results.txt (and, for ho3d, pred_mano.json) under out_dir -> the path of results.txt"""
         os.makedirs(out_dir, exist_ok=True)
@@ -345,6 +397,13 @@ class Evaluator:
             write_results(path, results, self.total, mesh=(self.mesh_err, self.mesh_err_al), fscores=(fs.T, fa.T, self.f_threshs))
         else:
             write_results(path, results, self.total)
+        if self.interaction:                                   # appended after everything results.txt has without the option
+            pen, con, vol, nv, n = self._iacc.tolist()
+            n = max(n, 1.0)
+            with open(path, "a") as f:
+                print("Interaction:", file=f)
+                print("penetration_depth=%.3f cm, contact_ratio=%.3f, intersection_volume=%.3f cm^3, contact_verts=%.1f"
+                      % (pen / n * 100.0, con / n, vol / n * 1.0e6, nv / n), file=f)
         if self.ho3d:
             if self.native:
                 joints = list(torch.cat(self.joint_list).cpu().numpy()) if self.joint_list else []

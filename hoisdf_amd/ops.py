@@ -2573,3 +2573,59 @@ def mesh_sdf_rows(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces, han
     call("hoisdf_mesh_sdf_rows", C.addressof(mh), C.addressof(mo), _p(lab), B, n_hand, n_obj, float(sigma[0]), float(sigma[1]),
          int(uniform_every), float(pad), float(clamp), int(seed) & 0x7FFFFFFFFFFFFFFF, _p(rows), 6, _p(ws), nws, _st())
     return rows
+
+
+# ---------------------------------------------------------------------------------------------
+# Hand-object interaction metrics (csrc/interact.hip, hoisdf_eval_interaction).  No gradient: these are evaluation numbers.
+# ---------------------------------------------------------------------------------------------
+@torch.no_grad()
+def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=None, obj_n_verts=None, contact_dist: float = 0.005,
+                     voxel: float = 0.005, want_mask: bool = False, hand_n_faces=None):
+    """hoisdf_eval_interaction: hand mesh (B, Vh, 3) with shared faces (Fh, 3) (per-sample (B, Fh, 3) with counts hand_n_faces (B,)
+    is taken too), object mesh (B, Vo, 3) with faces (B, Fo, 3) (or
+    shared (Fo, 3)), face counts obj_n_faces (B,) and vertex counts obj_n_verts (B,) or None; one frame, metres -> a dict of
+    per-sample tensors: pen_hand, pen_obj, min_dist, volume float32 (B,); contact_verts, in_contact, inside_count int32 (B,);
+    grid float32 (B, 8) = lo xyz, cell xyz, the bits of n_x | n_y << 8 | n_z << 16, 0; with want_mask also inside uint8
+    (B, 64^3): 1 where cell ix + n_x (iy + n_y iz) lies in both meshes, zero from n_x n_y n_z on.  want_mask may be that tensor:
+    it is written in place, and its bytes from n_x n_y n_z on are left as they are."""
+    hand_verts, obj_verts = hand_verts.contiguous().float(), obj_verts.contiguous().float()
+    _chk(hand_verts, obj_verts)
+    if hand_verts.dim() != 3 or obj_verts.dim() != 3 or obj_verts.shape[0] != hand_verts.shape[0] or hand_verts.shape[2] != 3 or obj_verts.shape[2] != 3:
+        raise ValueError(f"eval_interaction: hand {tuple(hand_verts.shape)} and object {tuple(obj_verts.shape)}: one (V, 3) mesh of each per sample")
+    dev, B = hand_verts.device, hand_verts.shape[0]
+    hf = hand_faces.to(dev, torch.int32).contiguous()
+    of = obj_faces.to(dev, torch.int32).contiguous()
+    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
+    ov = None if obj_n_verts is None else torch.as_tensor(obj_n_verts).to(dev, torch.int32).contiguous()
+    hn = None if hand_n_faces is None else torch.as_tensor(hand_n_faces).to(dev, torch.int32).contiguous()
+    if any(f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) for f in (hf, of)) or any(
+            n is not None and n.shape != (B,) for n in (on, ov, hn)):
+        raise ValueError("eval_interaction: faces (F, 3) or (B, F, 3), counts (B,)")
+    Vh, Vo, Fh, Fo = hand_verts.shape[1], obj_verts.shape[1], hf.shape[-2], of.shape[-2]
+    mh = _lib.Mesh(verts=hand_verts.data_ptr(), faces=hf.data_ptr(), n_faces=None if hn is None else hn.data_ptr(),
+                   face_batch_stride=0 if hf.dim() == 2 else 3 * Fh, V=Vh, max_faces=Fh)
+    mo = _lib.Mesh(verts=obj_verts.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
+                   face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=Vo, max_faces=Fo)
+    nws = lib().hoisdf_eval_interaction_workspace_bytes(B, Vh, Fh, Vo, Fo)
+    if nws < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    f32 = dict(device=dev, dtype=torch.float32)
+    i32 = dict(device=dev, dtype=torch.int32)
+    out = {"pen_hand": torch.empty(B, **f32), "pen_obj": torch.empty(B, **f32), "min_dist": torch.empty(B, **f32),
+           "contact_verts": torch.empty(B, **i32), "in_contact": torch.empty(B, **i32), "volume": torch.empty(B, **f32),
+           "inside_count": torch.empty(B, **i32), "grid": torch.empty(B, 8, **f32)}
+    cells = _lib.CONSTANTS["INTERACT_MAX_GRID"] ** 3
+    mask = None
+    if torch.is_tensor(want_mask):
+        mask = want_mask
+        if mask.shape != (B, cells) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev:
+            raise ValueError(f"eval_interaction: the mask must be a contiguous uint8 tensor of shape ({B}, {cells}) on {dev}")
+    elif want_mask:
+        mask = torch.zeros(B, cells, device=dev, dtype=torch.uint8)
+    call("hoisdf_eval_interaction", C.addressof(mh), C.addressof(mo), _p(ov), B, float(contact_dist), float(voxel), _p(out["pen_hand"]),
+         _p(out["pen_obj"]), _p(out["min_dist"]), _p(out["contact_verts"]), _p(out["in_contact"]), _p(out["volume"]),
+         _p(out["inside_count"]), _p(mask), _p(out["grid"]), _p(ws), nws, _st())
+    if mask is not None:
+        out["inside"] = mask
+    return out

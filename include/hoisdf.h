@@ -1139,6 +1139,48 @@ int hoisdf_mesh_sdf_rows(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const 
                          int n_obj, float sigma1, float sigma2, int uniform_every, float pad, float clamp, uint64_t seed,
                          float* rows, int ld, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- interaction: penetration depth, contact and intersection volume of a posed hand mesh and a posed object mesh ---------------
+ * reference: none - the reference evaluates every prediction against ground truth and never the hand against the object.  These
+ * are the three numbers hand-object work reports since ObMan (Hasson et al., CVPR 2019), at ObMan's 5 mm voxels.
+ * csrc/interact.hip; hoisdf_amd/interaction_oracle.py restates it in numpy.  Both meshes as hoisdf_mesh_sdf_rows takes them, in ONE
+ * frame, lengths in metres (volume: cubic metres); no gradient; fixed order everywhere: two calls give the same bits.
+ * hoisdf_eval_interaction (6 launches: hoisdf_mesh_prepare x 2, hoisdf_mesh_sdf x 2, the voxel pass, the per-sample reduction).
+ *   Checked before the first launch (HOISDF_ERR_INVALID, the argument named in hoisdf_last_error): hand, obj, verts, faces, a
+ *   required output or the workspace null; B < 0 or B > 65535; a mesh without vertices; max_faces > HOISDF_MESH_MAX_FACES; a
+ *   face_batch_stride that is neither 0 nor >= 3 max_faces; contact_dist < 0 or not finite; voxel <= 0 or not finite; a workspace
+ *   below hoisdf_eval_interaction_workspace_bytes(B, hand V, hand max_faces, obj V, obj max_faces) device bytes (-1 on an invalid
+ *   shape; 256-byte aligned).  B = 0 returns 0 with nothing launched.  It only enqueues on `stream`.
+ *   Vertex pass: sdf_obj(v) of every hand vertex to the object mesh and sdf_hand(v) of every object vertex to the hand mesh, by
+ *   hoisdf_mesh_sdf: its distance, its tie rule and its sign rule (winding > 0.5 is inside, so the hand's open wrist is handled;
+ *   a mesh without a usable face is 3e38 away).  obj_n_verts [B] DEVICE int32 (NULL: obj->V everywhere; clamped to 0 .. obj->V):
+ *   object vertex rows from obj_n_verts[b] on are padding and take no part in pen_obj.  They DO take part in the object's
+ *   bounding box, as every row of a hoisdf_mesh does: pad with copies of a real vertex.  Per sample, all [B]:
+ *     pen_hand       max over the hand vertices of max(0, -sdf_obj)
+ *     pen_obj        max over the sample's object vertices of max(0, -sdf_hand)
+ *     min_dist       min over the hand vertices of |sdf_obj|
+ *     contact_verts  int32: the number of hand vertices with sdf_obj <= contact_dist (a vertex inside the object counts)
+ *     in_contact     int32: 1 if contact_verts > 0 or pen_obj > 0, else 0
+ *   An object without a usable face: pen_hand = pen_obj = 0, contact_verts = in_contact = 0, min_dist = 3e38.
+ *   Voxel pass.  Grid rule, per sample and per axis, in fp32 and in this order, no product fused into a sum, from the two box[8]
+ *   of hoisdf_mesh_prepare (c = centre, h = half extent):  lo = max(c_hand - h_hand, c_obj - h_obj);  hi = min(c_hand + h_hand,
+ *   c_obj + h_obj);  extent = hi - lo;  n = min(ceil(extent / voxel), HOISDF_INTERACT_MAX_GRID), at least 1;  cell = extent / n:
+ *   the cells tile the overlap of the two bounding boxes exactly.  Any extent <= 0: n = 0 on every axis, no cell, volume 0.
+ *   Cell i = ix + n_x (iy + n_y iz) (ix fastest) has the centre lo + (ix + 0.5) cell (product, then sum).  For each centre only the
+ *   winding number against each mesh is taken (hoisdf_mesh_sdf's solid angles, its skipped-face rule, tiles of HOISDF_MESH_TILE
+ *   faces and a fixed summation order per centre); a cell is inside when winding_obj > 0.5 and winding_hand > 0.5.  The object comes
+ *   first, and a workgroup of 64 cells none of which is inside the object skips the hand.
+ *     inside_count   int32 [B]: the number of inside cells (integer sums: independent of any order)
+ *     volume         [B]: ((inside_count cell_x) cell_y) cell_z in fp32, cubic metres
+ *     inside_out     uint8 [B][HOISDF_INTERACT_MAX_GRID^3], may be NULL: 1 / 0 per cell i; bytes from n_x n_y n_z on are not touched
+ *     grid_out       [B][8] floats, may be NULL: lo xyz, cell xyz, n_x | n_y << 8 | n_z << 16 as int32 bits, 0 */
+#define HOISDF_INTERACT_MAX_GRID 64
+long hoisdf_eval_interaction_workspace_bytes(int B, int hand_V, int hand_max_faces, int obj_V, int obj_max_faces);
+int hoisdf_eval_interaction(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, int B,
+                            float contact_dist, float voxel,
+                            float* pen_hand, float* pen_obj, float* min_dist, int32_t* contact_verts, int32_t* in_contact,
+                            float* volume, int32_t* inside_count, uint8_t* inside_out, float* grid_out,
+                            void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

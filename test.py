@@ -38,6 +38,9 @@ def parse_args():
                     help="the IK variant's closed-form post-process as one HIP launch (hoisdf_ik_mano_fwd, cfg.native_ik)")
     ap.add_argument("--native-metrics", action="store_true",
                     help="the evaluation metrics through the hoisdf_eval_* entries, running sums on the device (cfg.native_metrics)")
+    ap.add_argument("--interaction", action="store_true",
+                    help="also report penetration depth, contact ratio and intersection volume of the predicted hand and object "
+                         "(hoisdf_eval_interaction, cfg.eval_interaction); the stand-in templates are then procedural MESHES")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -54,6 +57,7 @@ def main():
     cfg.native_ik = bool(a.native_ik)
     cfg.native_image = bool(a.native_image)
     cfg.native_metrics = bool(a.native_metrics)
+    cfg.eval_interaction = bool(a.interaction)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
@@ -66,7 +70,13 @@ def main():
     g = torch.Generator().manual_seed(0)
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
-    ev = M.Evaluator(cfg, templates, native=M.native_metrics_enabled(cfg))
+    faces = None
+    if M.interaction_enabled(cfg):                         # point clouds have no inside: closed procedural meshes instead
+        from hoisdf_amd.sdf_data import procedural_templates
+        faces = procedural_templates(device=dev)
+        templates = faces["verts"]
+    ev = M.Evaluator(cfg, templates, native=M.native_metrics_enabled(cfg), template_faces=faces,
+                     hand_faces=mano_layer.th_faces if faces is not None else None)
     for it, (inputs, targets, meta) in enumerate(loader):
         out = tester.predict(inputs, targets, meta, mano_layer=mano_layer)
         B = meta["mano_root"].shape[0]
