@@ -74,6 +74,14 @@ class Config:
     eval_interaction = False
     contact_dist = 0.005                 # metres: a hand vertex this close to the object (or inside it) is in contact
     interaction_voxel = 0.005            # metres: the cell of the intersection-volume grid (at most 64 cells per axis)
+    # not in the reference: the eval forward also extracts the zero level set of the two learned fields as triangle meshes
+    # (Model.field_surface: hoisdf_iso_extract, csrc/isosurf.hip) and test.py's Evaluator reports their Chamfer distance to the
+    # ground-truth MANO mesh and to the posed ground-truth template in a block appended to results.txt.  Also HOISDF_FIELD=1 /
+    # test.py --field-surface
+    eval_field = False
+    field_grid = 64                      # nodes per axis of the fine grid (the coarse one has half as many)
+    field_max_verts = 131072             # vertex rows per sample of the fixed-capacity outputs; twice as many face rows
+    field_samples = 4096                 # points drawn on the ground-truth surface for the gt -> prediction half
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

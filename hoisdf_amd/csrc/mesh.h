@@ -84,5 +84,8 @@ bool mesh_shape_ok(const char* what, int B, int V, int max_faces);
 void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long face_stride, const int32_t* n_faces, int max_faces,
                     const MeshBuffers& m, hipStream_t st);
 void launch_sdf(const MeshSdfArgs& a, int B, hipStream_t st);
+// N points per sample into points[b pstride + i ldp + 0..2] (hoisdf_mesh_sample_points; isosurf.hip draws its surface points with it)
+void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, int B, int N, float s1, float s2, int every, float pad,
+                   uint64_t seed, float* points, long pstride, int ldp, int32_t* face_out, hipStream_t st);
 
 }  // namespace hoisdf

@@ -273,7 +273,7 @@ void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long
   hipLaunchKernelGGL(mesh_prepare_kernel, dim3(B), dim3(256), 0, st, verts, V, faces, face_stride, n_faces, max_faces, m.tris, m.area,
                      m.cdf, m.box);
 }
-static void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, int B, int N, float s1, float s2, int every,
+void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, int B, int N, float s1, float s2, int every,
                           float pad, uint64_t seed, float* points, long pstride, int ldp, int32_t* face_out, hipStream_t st) {
   hipLaunchKernelGGL(mesh_sample_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, st, m.tris, m.cdf, m.box, n_faces, max_faces, N, s1, s2,
                      every, pad, seed, points, pstride, ldp, face_out);

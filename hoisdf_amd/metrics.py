@@ -20,6 +20,9 @@ Not in the reference: ``Evaluator(interaction=True)`` (``cfg.eval_interaction`` 
 also asks whether the PREDICTED hand and the PREDICTED object are compatible with each other - penetration depth, contact ratio and
 intersection volume, the numbers of ObMan and its successors - through hoisdf_eval_interaction (csrc/interact.hip, ops.eval_interaction)
 and appends them to results.txt.  Off by default: the file is then what the reference writes.
+``Evaluator(field=True)`` (``cfg.eval_field`` / ``HOISDF_FIELD=1`` / ``test.py --field-surface``) measures the zero level sets of the two
+learned fields (Model.field_surface: hoisdf_iso_extract, csrc/isosurf.hip) against the ground-truth meshes - the Chamfer distance of
+AlignSDF and gSDF, through hoisdf_eval_surface (ops.eval_surface) - and appends a ``Field:`` block after everything else.  Off by default.
 """
 from __future__ import annotations
 
@@ -205,6 +208,12 @@ def interaction_enabled(cfg=None) -> bool:
     return bool(getattr(cfg, "eval_interaction", False)) or os.environ.get("HOISDF_INTERACTION", "") == "1"
 
 
+def field_enabled(cfg=None) -> bool:
+    """cfg.eval_field (default False) or HOISDF_FIELD=1: the eval forward extracts the two field surfaces and the Evaluator appends
+    the Field block"""
+    return bool(getattr(cfg, "eval_field", False)) or os.environ.get("HOISDF_FIELD", "") == "1"
+
+
 class MeshEvalNative:
     """``MeshEval`` on the device (hoisdf_eval_accum_*): one fp64 sum per vertex and one count per (threshold, vertex) instead of
     every distance of the test set on the host.  The thresholds are fixed when the object is made, since the counts are taken as
@@ -260,16 +269,29 @@ class Evaluator:
     turned and moved by the mean predicted rotation and translation + obj_center_cam - runs ops.eval_interaction on it (cfg.contact_dist,
     cfg.interaction_voxel) and keeps running sums on the device; ``write`` appends one block after everything else.  It needs the
     templates as meshes: ``template_faces`` = the ``faces`` (T,F,3) / ``n_faces`` (T,) of sdf_data.pack_templates (whose ``verts`` are
-    ``templates``), and ``hand_faces`` (Fh,3) = the MANO layer's ``th_faces``.  Samples with obj_cls < 0 are not evaluated."""
+    ``templates``), and ``hand_faces`` (Fh,3) = the MANO layer's ``th_faces``.  Samples with obj_cls < 0 are not evaluated.
+    ``field=True`` (or cfg.eval_field / HOISDF_FIELD=1; either backend): where a batch carries the ground-truth MANO mesh (the
+    condition of the mesh block) and the field surfaces of the eval forward (``field_{hand,obj}_verts`` / ``_n_verts`` / ``_n_faces``,
+    Model.field_surface), every ``feed`` runs ops.eval_surface of the hand surface against the ground-truth MANO mesh + mano_root and
+    of the object surface against the template posed by the GROUND-TRUTH rotation and translation + obj_center_cam
+    (cfg.field_samples points), keeps running sums on the device, and ``write`` appends one ``Field:`` block after everything else:
+    the mean Chamfer distances in cm^2 over the samples that took part and the share of samples left out - a surface without a
+    vertex, one that overflowed its capacity, a ground-truth mesh without area, for the object also obj_cls < 0.  It needs the same
+    ``template_faces`` / ``hand_faces``."""
 
     def __init__(self, cfg, templates: torch.Tensor, native: bool = False, interaction: bool = False,
-                 template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None):
+                 template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None, field: bool = False):
         self.cfg, self.templates, self.native = cfg, templates, bool(native)
         self.dev = templates.device
         self.interaction = bool(interaction) or interaction_enabled(cfg)
-        if self.interaction:
+        self.field = bool(field) or field_enabled(cfg)
+        if self.field:
+            # per field (hand, obj): the sum of the Chamfer distances [m^2] over the samples that took part, their number, the samples seen
+            self._facc = torch.zeros(2, 3, device=self.dev, dtype=torch.float64)
+        if self.interaction or self.field:
             if template_faces is None or hand_faces is None or "faces" not in template_faces:
-                raise ValueError("Evaluator(interaction=True) needs template_faces (faces, n_faces of sdf_data.pack_templates) and hand_faces")
+                raise ValueError("Evaluator(interaction=True) / Evaluator(field=True) needs template_faces (faces, n_faces of "
+                                 "sdf_data.pack_templates) and hand_faces")
             self._tfaces = torch.as_tensor(template_faces["faces"]).to(self.dev, torch.int32)
             n = template_faces.get("n_faces")
             self._tn = torch.full((self._tfaces.shape[0],), self._tfaces.shape[1], dtype=torch.int32) if n is None else torch.as_tensor(n)
@@ -277,6 +299,7 @@ class Evaluator:
             self._hfaces = torch.as_tensor(hand_faces).to(self.dev, torch.int32)
             if self._tfaces.dim() != 3 or self._tfaces.shape[0] != templates.shape[0] or self._tn.shape != (templates.shape[0],):
                 raise ValueError(f"template_faces {tuple(self._tfaces.shape)} for {templates.shape[0]} templates")
+        if self.interaction:
             # the sums of max(pen_hand, pen_obj) [m], in_contact, volume [m^3], contact_verts over the evaluated samples, their number
             self._iacc = torch.zeros(5, device=self.dev, dtype=torch.float64)
         self.ho3d = cfg.dataset == "ho3d"
@@ -341,6 +364,8 @@ class Evaluator:
             pj, gj = out["mano_joints_out"], out["mano_joints_gt_out"]
         mje, pamje = ops.eval_hand_joints(pj, gj)[:2] if self.native else eval_hand_joint(pj, gj)
         self._add({"ADDS_error": om["ADDS"], "mano_mje": mje, "mano_pamje": pamje, "OCE_error": om["OCE"], "MCE_error": om["MCE"]}, B, used)
+        if self.field and cfg.eval_mesh and "mano_mesh_gt_out" in out and "field_hand_verts" in out:
+            self._feed_field(out, tg, meta, obj_cls)
         if cfg.eval_mesh and "mano_mesh_out" in out:
             pv, gv = out["mano_mesh_out"], out["mano_mesh_gt_out"]
             if self.native:
@@ -378,6 +403,33 @@ class Evaluator:
                             r["contact_verts"].double(), torch.ones_like(r["volume"]).double()])
         self._iacc += (vals * used.double()[None]).sum(1)
 
+    def field_per_sample(self, out, targets, meta, obj_cls):
+        """ops.eval_surface of the two field surfaces of every sample -> {"hand": (its dict, used (B,) bool), "obj": ...}; used: the
+        sample took part (n_used > 0, no overflowed capacity, for the object obj_cls >= 0)"""
+        from . import ops
+        dev = self.dev
+        root = meta["mano_root"].to(dev)
+        cls = torch.as_tensor(obj_cls).to(dev).long()
+        known = cls >= 0
+        cls = cls.clamp_min(0)
+        gt_hand = out["mano_mesh_gt_out"].detach() + root[:, None]
+        R = batch_rodrigues(targets["obj_rot"].to(dev).reshape(-1, 3))
+        gt_obj = self.templates[cls] @ R.transpose(1, 2) + (targets["rel_obj_trans"].to(dev).reshape(-1, 3) + meta["obj_center_cam"].to(dev))[:, None]
+        res = {}
+        for kind, gv, gf, gn, ok in (("hand", gt_hand, self._hfaces, None, torch.ones_like(known)),
+                                     ("obj", gt_obj, self._tfaces[cls], self._tn[cls], known)):
+            v, nv, nf = out[f"field_{kind}_verts"], out[f"field_{kind}_n_verts"], out[f"field_{kind}_n_faces"]
+            r = ops.eval_surface(v, nv, gv, gf, gn, int(getattr(self.cfg, "field_samples", 4096)), seed=self.total)
+            fits = (nv <= v.shape[1]) & (nf <= out[f"field_{kind}_faces"].shape[1])
+            res[kind] = (r, ok & fits & (r["n_used"] > 0))
+        return res
+
+    def _feed_field(self, out, targets, meta, obj_cls) -> None:
+        res = self.field_per_sample(out, targets, meta, obj_cls)
+        self._facc += torch.stack([torch.stack([(r["chamfer"].double() * used.double()).sum(), used.double().sum(),
+                                                torch.tensor(float(used.numel()), device=self.dev, dtype=torch.float64)])
+                                   for r, used in (res["hand"], res["obj"])])
+
     def write(self, out_dir: str) -> str:
         """results.txt (and, for ho3d, pred_mano.json) under out_dir -> the path of results.txt"""
         os.makedirs(out_dir, exist_ok=True)
@@ -404,6 +456,12 @@ class Evaluator:
                 print("Interaction:", file=f)
                 print("penetration_depth=%.3f cm, contact_ratio=%.3f, intersection_volume=%.3f cm^3, contact_verts=%.1f"
                       % (pen / n * 100.0, con / n, vol / n * 1.0e6, nv / n), file=f)
+        if self.field:                                         # after everything else, the interaction block included
+            (hs, hn, ht), (os_, on, ot) = self._facc.tolist()
+            with open(path, "a") as f:
+                print("Field:", file=f)
+                print("hand_chamfer=%.4f cm^2, obj_chamfer=%.4f cm^2, hand_left_out=%.3f, obj_left_out=%.3f"
+                      % (hs / max(hn, 1.0) * 1.0e4, os_ / max(on, 1.0) * 1.0e4, 1.0 - hn / max(ht, 1.0), 1.0 - on / max(ot, 1.0)), file=f)
         if self.ho3d:
             if self.native:
                 joints = list(torch.cat(self.joint_list).cpu().numpy()) if self.joint_list else []

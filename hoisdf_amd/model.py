@@ -297,6 +297,69 @@ class Model(nn.Module):
             pose_class = self.sdf_forward(pyr, pose_points, center_joint, cam_intr, sdf_scale, type)[1]
         return pose_points, pose_sdf, pose_pe, pose_class
 
+    FIELD_CHUNK_ROWS = 262144      # rows of one hoisdf_sdf_query_fwd call of field_surface: one 64^3 sample, 1 GB of gathered rows at C = 992
+
+    @torch.no_grad()
+    def field_surface(self, feature_pyramid, meta_info, kind="hand", n=64, coarse_n=32, box=None, return_values=False, *,
+                      max_verts=None, max_faces=None, chunk_rows=None):
+        """The zero level set of the learned hand / object field as an indexed triangle mesh in camera metres (include/hoisdf.h
+        "iso-surface"; no reference counterpart).  Coarse grid of ``coarse_n`` nodes per axis over the lattice cube [-1, 1]^3 of
+        the scaled frame (``box`` (B, 2, 3): that region per sample instead) -> the field on its nodes -> hoisdf_iso_refine_grid
+        (pad 1: the box of the inside nodes, no host read) -> the field on the ``n`` fine nodes per axis -> hoisdf_iso_extract at
+        level 0 of sdf_raw (the unclamped tanh sdf_infer ranks on), vertices stored as x / scale + centre.
+        Decoder dropout is off whatever the module's mode.  The queries go in chunks of at most FIELD_CHUNK_ROWS = 262144 rows with
+        their sample index (``chunk_rows`` overrides it), of equal size up to a multiple of 256, so hoisdf_sdf_query_workspace stays
+        bounded: a gathered row is 4 KB at C = 992, and 22 x 64^3 rows at once would be 23 GB.
+        -> (verts (B, max_verts, 3), faces (B, max_faces, 3) int32, n_verts (B,), n_faces (B,) int32: the counts needed) as
+        ops.iso_surface returns them: with both capacities given nothing synchronises.  With ``return_values`` a fifth element,
+        a dict: values (B, n^3), grid (B, 8), coarse_values (B, coarse_n^3), coarse_grid (B, 8), all in the scaled frame."""
+        c = self.cfg
+        if kind not in ("hand", "obj"):
+            raise ValueError(f"field_surface: kind={kind!r} ('hand' or 'obj')")
+        pyr = self._pyramid(feature_pyramid)
+        center = (meta_info["mano_root"] if kind == "hand" else meta_info["obj_center_cam"]).reshape(-1, 3).contiguous().float()
+        scale = c.hand_sdf_scale if kind == "hand" else c.obj_sdf_scale
+        K, B, dev = meta_info["cam_intr"], center.shape[0], center.device
+        weights = self._query_weights(kind)
+        chunk = int(chunk_rows or self.FIELD_CHUNK_ROWS)
+
+        def field(grid, nodes):
+            pts, idx = ops.iso_grid_points(grid, nodes)
+            rows = pts.shape[0]
+            parts = max(1, -(-rows // chunk))
+            per = -(-(-(-rows // parts)) // 256) * 256
+            raw = torch.empty(rows, device=dev)
+            for s in range(0, rows, per):
+                raw[s:s + per] = ops.sdf_query(weights, pyr, pts[s:s + per], center, K, scale, c.ClampingDistance, c.input_img_shape,
+                                               idx[s:s + per], drop_p=0.0)[1]
+            return raw.view(B, nodes ** 3)
+
+        lo = torch.full((B, 3), -1.0, device=dev) if box is None else box[:, 0].to(dev).float()
+        hi = torch.full((B, 3), 1.0, device=dev) if box is None else box[:, 1].to(dev).float()
+        coarse_grid = torch.cat([lo, (hi - lo) / float(coarse_n - 1), torch.zeros(B, 2, device=dev)], 1)
+        coarse = field(coarse_grid, coarse_n)
+        grid = ops.iso_refine_grid(coarse, coarse_grid, coarse_n, 0.0, 1, n)
+        values = field(grid, n)
+        res = ops.iso_surface(values, grid, n, 0.0, max_verts, max_faces, out_scale=1.0 / scale, out_shift=center)
+        if return_values:
+            return res + ({"values": values, "grid": grid, "coarse_values": coarse, "coarse_grid": coarse_grid},)
+        return res
+
+    def field_enabled(self) -> bool:
+        """cfg.eval_field (default False) or HOISDF_FIELD=1: the eval forward adds the two field surfaces to its outputs"""
+        return bool(getattr(self.cfg, "eval_field", False)) or os.environ.get("HOISDF_FIELD", "") == "1"
+
+    def _field_outputs(self, out, feature_pyramid, meta_info):
+        """the opt-in outputs of the eval forward: field_{hand,obj}_{verts,faces,n_verts,n_faces} in fixed-capacity tensors
+        (cfg.field_max_verts vertex rows, twice as many face rows; the counts are the needs: a count above its capacity marks an
+        overflowed sample).  Nothing synchronises."""
+        c = self.cfg
+        mv = int(c.field_max_verts)
+        for kind in ("hand", "obj"):
+            v, f, nv, nf = self.field_surface(feature_pyramid, meta_info, kind, int(c.field_grid), max(int(c.field_grid) // 2, 2),
+                                              max_verts=mv, max_faces=2 * mv)
+            out.update({f"field_{kind}_verts": v, f"field_{kind}_faces": f, f"field_{kind}_n_verts": nv, f"field_{kind}_n_faces": nf})
+
     def render_gaussian_heatmap(self, joint_coord):
         """reference :128-143 (encoder-side auxiliary target; plain torch)."""
         c = self.cfg
@@ -687,7 +750,10 @@ class Model(nn.Module):
             else:
                 img_feat, skips = self.backbone_net(inputs["img"])
                 feature_pyramid, decoder_out = self.decoder_net(img_feat, skips)
-            out = self.infer_native(self._pyramid(feature_pyramid), meta_info, counts)
+            pyr = self._pyramid(feature_pyramid)
+            out = self.infer_native(pyr, meta_info, counts)
+            if self.field_enabled():
+                self._field_outputs(out, pyr, meta_info)
             if c.dataset == "dexycb":
                 if not c.use_inverse_kinematics:
                     gv, gj, _ = ops.mano_gt(targets["mano_param"], self.mano_head.mano_layer.kernel_assets())
@@ -707,6 +773,8 @@ class Model(nn.Module):
         pyr = self._pyramid(feature_pyramid)
         self._set_arithmetic(f16_eval=mode != "train")
         loss, out = self.hot_path(pyr, inputs, targets, meta_info, mode, epoch_cnt, batch_ratio, branch_a, infer_counts)
+        if mode != "train" and not self.training and self.field_enabled():
+            self._field_outputs(out, pyr, meta_info)
         if mode == "train" or c.dataset == "dexycb":                                   # :404-422 aux image losses
             self._aux_outputs(out, targets, decoder_out)
             # (f4) one HIP pass: Gaussian heat-map target + MSE + the two BCE maps

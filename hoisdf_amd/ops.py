@@ -2629,3 +2629,120 @@ def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=N
     if mask is not None:
         out["inside"] = mask
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Surface from a sampled field (csrc/isosurf.hip, the hoisdf_iso_* entries and hoisdf_eval_surface).  No gradient.
+# ---------------------------------------------------------------------------------------------
+def _iso_grid(grid, n: int):
+    grid = grid.contiguous().float()
+    _chk(grid)
+    if grid.dim() != 2 or grid.shape[1] != 8:
+        raise ValueError(f"iso: grid {tuple(grid.shape)} must be (B, 8) = lo xyz, cell xyz, 0, 0")
+    if not 2 <= int(n) <= _lib.CONSTANTS["ISO_MAX_GRID"]:
+        raise ValueError(f"iso: n={n} (2 .. {_lib.CONSTANTS['ISO_MAX_GRID']})")
+    return grid, grid.shape[0], int(n) ** 3
+
+
+def _iso_values(values, B: int, N: int, what: str):
+    """(B, n^3) float32 view whose rows follow each other, any element stride (a column of a wider row block) -> (view, ld)"""
+    if values.dim() != 2 or values.shape != (B, N) or values.dtype != torch.float32 or values.stride(1) < 1 or \
+            (B > 1 and values.stride(0) != N * values.stride(1)):
+        values = values.reshape(B, N).float().contiguous()
+    _chk(values)
+    return values, values.stride(1)
+
+
+@torch.no_grad()
+def iso_grid_points(grid, n: int, with_sample_idx: bool = True):
+    """grid (B, 8) -> points (B n^3, 3) [, sample_idx (B n^3,) int32]: the node positions as rows for sdf_query"""
+    grid, B, N = _iso_grid(grid, n)
+    pts = torch.empty(B * N, 3, device=grid.device, dtype=torch.float32)
+    idx = torch.empty(B * N, device=grid.device, dtype=torch.int32) if with_sample_idx else None
+    call("hoisdf_iso_grid_points", _p(grid), int(n), B, _p(pts), _p(idx), _st())
+    return (pts, idx) if with_sample_idx else pts
+
+
+@torch.no_grad()
+def iso_refine_grid(values, grid, n: int, iso: float = 0.0, pad_cells: int = 1, n_out: Optional[int] = None):
+    """values (B, n^3) on grid (B, 8) -> the (B, 8) grid of n_out nodes over the index box of the nodes below iso, grown by
+    pad_cells and clipped to the coarse grid (a sample without such a node: the coarse grid re-divided).  No host read."""
+    grid, B, N = _iso_grid(grid, n)
+    values, ld = _iso_values(values, B, N, "iso_refine_grid")
+    out = torch.empty(B, 8, device=grid.device, dtype=torch.float32)
+    call("hoisdf_iso_refine_grid", _p(values), ld, _p(grid), int(n), B, float(iso), int(pad_cells), int(n if n_out is None else n_out),
+         _p(out), _st())
+    return out
+
+
+@torch.no_grad()
+def iso_surface(values, grid, n: int, iso: float = 0.0, max_verts: Optional[int] = None, max_faces: Optional[int] = None,
+                out_scale: Optional[float] = None, out_shift=None):
+    """hoisdf_iso_extract: values (B, n^3) on grid (B, 8) -> (verts (B, max_verts, 3), faces (B, max_faces, 3) int32, n_verts (B,),
+    n_faces (B,) int32): the counts NEEDED; rows beyond them are not written (zero here), and a sample whose count exceeds a
+    capacity is overflowed - its written faces keep their true vertex ids.  With both capacities given nothing synchronises;
+    a capacity left None is sized from one count-only call and one read of the counts (exact allocation).  out_scale /
+    out_shift (B, 3): the stored vertex is x * out_scale + out_shift."""
+    grid, B, N = _iso_grid(grid, n)
+    values, ld = _iso_values(values, B, N, "iso_surface")
+    dev = grid.device
+    shift = None
+    if out_shift is not None or out_scale is not None:
+        shift = torch.zeros(B, 3, device=dev, dtype=torch.float32) if out_shift is None else out_shift.reshape(B, 3).contiguous().float()
+        _chk(shift)
+    scale = 1.0 if out_scale is None else float(out_scale)
+    nws = lib().hoisdf_iso_extract_workspace_bytes(B, int(n))
+    if nws < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    nv = torch.zeros(B, device=dev, dtype=torch.int32)
+    nf = torch.zeros(B, device=dev, dtype=torch.int32)
+
+    def run(verts, faces, mv, mf):
+        call("hoisdf_iso_extract", _p(values), ld, _p(grid), int(n), B, float(iso), scale, _p(shift), _p(verts), mv, _p(faces), mf,
+             _p(nv), _p(nf), _p(ws), nws, _st())
+
+    if max_verts is None or max_faces is None:
+        run(None, None, 0, 0)
+        counts = torch.stack([nv, nf]).amax(1).tolist() if B else [0, 0]      # the one sized read-back
+        max_verts = counts[0] if max_verts is None else max_verts
+        max_faces = counts[1] if max_faces is None else max_faces
+    verts = torch.zeros(B, int(max_verts), 3, device=dev, dtype=torch.float32)
+    faces = torch.zeros(B, int(max_faces), 3, device=dev, dtype=torch.int32)
+    run(verts, faces, int(max_verts), int(max_faces))
+    return verts, faces, nv, nf
+
+
+@torch.no_grad()
+def eval_surface(pred_verts, pred_n_verts, gt_verts, gt_faces, gt_n_faces=None, n_samples: int = 2048, seed: int = 0,
+                 extras: bool = False):
+    """hoisdf_eval_surface: predicted vertices (B, max_verts, 3) with counts (B,) against the ground-truth mesh gt_verts (B, V, 3),
+    gt_faces (F, 3) shared or (B, F, 3) with counts gt_n_faces -> a dict of (B,) tensors: pred_to_gt, gt_to_pred, chamfer (mean
+    squared distances, square metres) and n_used int32 (0: the sample has no predicted vertex or no usable face, and zeros).
+    With extras also samples (B, n_samples, 3), the points drawn on the ground-truth surface, and nearest (B, n_samples) int32."""
+    pred_verts, gt_verts = pred_verts.contiguous().float(), gt_verts.contiguous().float()
+    _chk(pred_verts, gt_verts)
+    if pred_verts.dim() != 3 or gt_verts.dim() != 3 or pred_verts.shape[2] != 3 or gt_verts.shape[2] != 3 or gt_verts.shape[0] != pred_verts.shape[0]:
+        raise ValueError(f"eval_surface: predicted {tuple(pred_verts.shape)} and ground truth {tuple(gt_verts.shape)}: (B, ., 3) each")
+    dev, B, mv = pred_verts.device, pred_verts.shape[0], pred_verts.shape[1]
+    pn = torch.as_tensor(pred_n_verts).to(dev, torch.int32).contiguous()
+    gf = gt_faces.to(dev, torch.int32).contiguous()
+    gn = None if gt_n_faces is None else torch.as_tensor(gt_n_faces).to(dev, torch.int32).contiguous()
+    if pn.shape != (B,) or gf.dim() not in (2, 3) or gf.shape[-1] != 3 or (gf.dim() == 3 and gf.shape[0] != B) or (gn is not None and gn.shape != (B,)):
+        raise ValueError("eval_surface: counts (B,), faces (F, 3) or (B, F, 3)")
+    F = gf.shape[-2]
+    m = _lib.Mesh(verts=gt_verts.data_ptr(), faces=gf.data_ptr(), n_faces=None if gn is None else gn.data_ptr(),
+                  face_batch_stride=0 if gf.dim() == 2 else 3 * F, V=gt_verts.shape[1], max_faces=F)
+    nws = lib().hoisdf_eval_surface_workspace_bytes(B, mv, F, int(n_samples))
+    if nws < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    out = {"pred_to_gt": torch.empty(B, device=dev, dtype=torch.float32), "gt_to_pred": torch.empty(B, device=dev, dtype=torch.float32),
+           "chamfer": torch.empty(B, device=dev, dtype=torch.float32), "n_used": torch.empty(B, device=dev, dtype=torch.int32)}
+    samples = torch.empty(B, int(n_samples), 3, device=dev, dtype=torch.float32) if extras else None
+    nearest = torch.empty(B, int(n_samples), device=dev, dtype=torch.int32) if extras else None
+    call("hoisdf_eval_surface", _p(pred_verts), _p(pn), mv, C.addressof(m), B, int(n_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         _p(out["pred_to_gt"]), _p(out["gt_to_pred"]), _p(out["chamfer"]), _p(out["n_used"]), _p(samples), _p(nearest), _p(ws), nws, _st())
+    if extras:
+        out["samples"], out["nearest"] = samples, nearest
+    return out

@@ -41,6 +41,9 @@ def parse_args():
     ap.add_argument("--interaction", action="store_true",
                     help="also report penetration depth, contact ratio and intersection volume of the predicted hand and object "
                          "(hoisdf_eval_interaction, cfg.eval_interaction); the stand-in templates are then procedural MESHES")
+    ap.add_argument("--field-surface", action="store_true",
+                    help="also extract the zero level set of the two learned fields (Model.field_surface, hoisdf_iso_extract) and report "
+                         "their Chamfer distance to the ground-truth meshes (cfg.eval_field); procedural MESHES as templates")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -58,6 +61,7 @@ def main():
     cfg.native_image = bool(a.native_image)
     cfg.native_metrics = bool(a.native_metrics)
     cfg.eval_interaction = bool(a.interaction)
+    cfg.eval_field = bool(a.field_surface)
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
@@ -71,7 +75,7 @@ def main():
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
     faces = None
-    if M.interaction_enabled(cfg):                         # point clouds have no inside: closed procedural meshes instead
+    if M.interaction_enabled(cfg) or M.field_enabled(cfg):   # point clouds have no inside and no surface: closed procedural meshes instead
         from hoisdf_amd.sdf_data import procedural_templates
         faces = procedural_templates(device=dev)
         templates = faces["verts"]
