@@ -82,6 +82,19 @@ class Config:
     field_grid = 64                      # nodes per axis of the fine grid (the coarse one has half as many)
     field_max_verts = 131072             # vertex rows per sample of the fixed-capacity outputs; twice as many face rows
     field_samples = 4096                 # points drawn on the ground-truth surface for the gt -> prediction half
+    # not in the reference: the mesh rasteriser (hoisdf_raster_meshes, csrc/raster.hip; hoisdf_amd/render.py), three uses, all off:
+    #   seg_source = "mesh" (also HOISDF_SEG=mesh / Trainer(seg_source=...)): the trainer renders targets["hand_seg"] / ["obj_seg"] each
+    #     step from the step's own label meshes through meta["cam_intr"] - the modal silhouettes, mutual occlusion included - instead
+    #     of taking them from per-frame mask files; with sdf_source = "mesh" both share one MeshSdfSource.  "" = off
+    #   eval_silhouette (also HOISDF_SILHOUETTE=1 / Evaluator(silhouette=True) / test.py --silhouette): results.txt gains a block
+    #     with the mean IoU of the predicted hand's and the predicted object's rendered silhouettes against the mask targets
+    #   overlay_dir (test.py --overlay DIR): one image per sample, the predicted pair blended over the input crop
+    seg_source = ""
+    eval_silhouette = False
+    overlay_dir = ""
+    raster_half_pixel = False            # False: pixel (px, py) is sampled at (px, py), the OpenCV convention of the 2D labels
+    raster_near = 0.01                   # metres: a face with a corner nearer than this is dropped (no clipping)
+    overlay_alpha = 160                  # of 256: the weight of the mesh colour over the image
     # not in the reference: run the object transformer stack on a second HIP stream next to the hand stack
     overlap_streams = True
     resnet_type = 50

@@ -101,19 +101,22 @@ class SyntheticMeshSdfDataset(torch.utils.data.Dataset):
     at all - ``mano_param``, ``obj_rot``, ``rel_obj_trans`` (targets), ``mano_root``, ``obj_center_cam`` and ``obj_cls`` = the
     object's template (meta_info) are what the points and their distances are computed from on the device, every step anew"""
 
-    def __init__(self, cfg: Config, n_templates: int, length: int = 64, seed: int = 0):
+    def __init__(self, cfg: Config, n_templates: int, length: int = 64, seed: int = 0, keep_points: bool = False):
         self.cfg, self.n_templates, self.length, self.seed = cfg, n_templates, length, seed
+        self.keep_points = keep_points      # for Trainer(seg_source=...) without an SDF source: the point sets and SDF targets stay
 
     def __len__(self):
         return self.length
 
     def __getitem__(self, i):
-        ins, tg, mt = T.synthetic_batch(1, 1, 1, seed=self.seed * 100003 + i)
+        n = (self.cfg.num_samp_hand, self.cfg.num_samp_obj) if self.keep_points else (1, 1)
+        ins, tg, mt = T.synthetic_batch(1, n[0], n[1], seed=self.seed * 100003 + i)
         sq = lambda d: {k: v[0] for k, v in d.items()}
         ins, tg, mt = sq(ins), sq(tg), sq(mt)
-        for k in ("hand_sdf_points", "obj_sdf_points", "hand_pre_points", "obj_pre_points"):
-            ins.pop(k)
-        tg.pop("hand_sdf"), tg.pop("obj_sdf")
+        if not self.keep_points:
+            for k in ("hand_sdf_points", "obj_sdf_points", "hand_pre_points", "obj_pre_points"):
+                ins.pop(k)
+            tg.pop("hand_sdf"), tg.pop("obj_sdf")
         mt["obj_cls"] = torch.tensor((self.seed + i) % self.n_templates)
         return ins, tg, mt
 
@@ -247,8 +250,9 @@ def load_reference_state_dict(model: torch.nn.Module, network: Dict[str, torch.T
 
 class Trainer:
     def __init__(self, cfg: Config, device: torch.device, dataset=None, batch_size: Optional[int] = None,
-                 channels_last: bool = True, tune_encoder: bool = True, sdf_store=None, sdf_source=None):
+                 channels_last: bool = True, tune_encoder: bool = True, sdf_store=None, sdf_source=None, seg_source=None):
         self.cfg, self.device = cfg, device
+        self.seg_source = seg_source        # the two mask targets rendered from the batch's meshes (render.MeshSegSource)
         self.sdf_store = sdf_store          # (f2) HBM-resident sdf_processed rows: the query points are drawn on the device
         self.sdf_source = sdf_source        # no rows at all: points and distances computed from the batch's meshes (MeshSdfSource)
         self._sdf_draws = 0
@@ -284,10 +288,21 @@ class Trainer:
                 head = getattr(self.model, "mano_head", None)
                 layer = head.mano_layer if head is not None else self.model.ik_mano_layer
                 self.sdf_source = MeshSdfSource(layer, procedural_templates(), cfg)
+        if self.seg_source is None:
+            from .render import MeshSegSource, seg_from_mesh
+            if seg_from_mesh(cfg):          # cfg.seg_source = "mesh" / HOISDF_SEG=mesh without a source: the SDF source's meshes, else the same stand-ins
+                src = self.sdf_source
+                if src is None:
+                    from .sdf_data import MeshSdfSource, procedural_templates
+                    head = getattr(self.model, "mano_head", None)
+                    src = MeshSdfSource(head.mano_layer if head is not None else self.model.ik_mano_layer, procedural_templates(), cfg)
+                self.seg_source = MeshSegSource(src, cfg)
         if dataset is None and sdf_store is not None:
             dataset = SyntheticSdfDataset(cfg, sdf_store.n_frames, seed=self.rank)
         elif dataset is None and self.sdf_source is not None:
             dataset = SyntheticMeshSdfDataset(cfg, self.sdf_source.n_templates, seed=self.rank)
+        elif dataset is None and self.seg_source is not None:      # the full synthetic sample + the template its masks are rendered from
+            dataset = SyntheticMeshSdfDataset(cfg, self.seg_source.n_templates, seed=self.rank, keep_points=True)
         ds = dataset if dataset is not None else SyntheticDataset(cfg, seed=self.rank)
         bs = batch_size or cfg.train_batch_size
         sampler = torch.utils.data.distributed.DistributedSampler(ds, self.world, self.rank, shuffle=True) \
@@ -339,6 +354,8 @@ class Trainer:
             for k in ("hand_sdf_points", "obj_sdf_points", "hand_pre_points", "obj_pre_points"):
                 inputs[k] = pts[k]
             targets["hand_sdf"], targets["obj_sdf"] = pts["hand_sdf"], pts["obj_sdf"]
+        if self.seg_source is not None:
+            self.seg_source.fill(targets, meta)                   # hand_seg / obj_seg: the silhouettes of the step's own label meshes
         if self.channels_last:
             inputs["img"] = inputs["img"].contiguous(memory_format=torch.channels_last)
         self.reducer.zero_grad()

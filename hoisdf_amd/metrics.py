@@ -23,6 +23,9 @@ and appends them to results.txt.  Off by default: the file is then what the refe
 ``Evaluator(field=True)`` (``cfg.eval_field`` / ``HOISDF_FIELD=1`` / ``test.py --field-surface``) measures the zero level sets of the two
 learned fields (Model.field_surface: hoisdf_iso_extract, csrc/isosurf.hip) against the ground-truth meshes - the Chamfer distance of
 AlignSDF and gSDF, through hoisdf_eval_surface (ops.eval_surface) - and appends a ``Field:`` block after everything else.  Off by default.
+``Evaluator(silhouette=True)`` (``cfg.eval_silhouette`` / ``HOISDF_SILHOUETTE=1`` / ``test.py --silhouette``) renders the predicted pair
+with mutual occlusion (hoisdf_raster_meshes, csrc/raster.hip) and appends a ``Silhouette:`` block - the IoU of its two modal masks against
+the mask targets - after everything else.  Off by default.
 """
 from __future__ import annotations
 
@@ -208,6 +211,11 @@ def interaction_enabled(cfg=None) -> bool:
     return bool(getattr(cfg, "eval_interaction", False)) or os.environ.get("HOISDF_INTERACTION", "") == "1"
 
 
+def silhouette_enabled(cfg=None) -> bool:
+    """cfg.eval_silhouette (default False) or HOISDF_SILHOUETTE=1: the Evaluator appends the silhouette block"""
+    return bool(getattr(cfg, "eval_silhouette", False)) or os.environ.get("HOISDF_SILHOUETTE", "") == "1"
+
+
 def field_enabled(cfg=None) -> bool:
     """cfg.eval_field (default False) or HOISDF_FIELD=1: the eval forward extracts the two field surfaces and the Evaluator appends
     the Field block"""
@@ -277,21 +285,34 @@ class Evaluator:
     (cfg.field_samples points), keeps running sums on the device, and ``write`` appends one ``Field:`` block after everything else:
     the mean Chamfer distances in cm^2 over the samples that took part and the share of samples left out - a surface without a
     vertex, one that overflowed its capacity, a ground-truth mesh without area, for the object also obj_cls < 0.  It needs the same
-    ``template_faces`` / ``hand_faces``."""
+    ``template_faces`` / ``hand_faces``.
+    ``silhouette=True`` (or cfg.eval_silhouette / HOISDF_SILHOUETTE=1; either backend): every ``feed`` renders the predicted pair
+    (render.predicted_pair, the pair of the interaction block) with mutual occlusion through meta["cam_intr"] at cfg.input_img_shape
+    (ops.raster_meshes), folds the two modal masks to the shape of targets["hand_seg"] / ["obj_seg"] and counts intersection and
+    union against them on the device (ops.eval_silhouette); ``write`` reads the integer counts once, divides in float64 on the host
+    and appends one ``Silhouette:`` block after everything else: the mean IoU of the hand and of the object over the samples that
+    took part and the share of samples left out - an empty union, or obj_cls < 0.  It needs the same ``template_faces`` /
+    ``hand_faces``."""
 
     def __init__(self, cfg, templates: torch.Tensor, native: bool = False, interaction: bool = False,
-                 template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None, field: bool = False):
+                 template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None,
+                 silhouette: bool = False, field: bool = False):
         self.cfg, self.templates, self.native = cfg, templates, bool(native)
         self.dev = templates.device
         self.interaction = bool(interaction) or interaction_enabled(cfg)
         self.field = bool(field) or field_enabled(cfg)
+        self.silhouette = bool(silhouette) or silhouette_enabled(cfg)
+        self._hfaces = None
+        if self.silhouette:
+            self._scounts = []          # per feed: int32 (B, 5) on the device = the four counts of ops.eval_silhouette, obj_cls >= 0
         if self.field:
             # per field (hand, obj): the sum of the Chamfer distances [m^2] over the samples that took part, their number, the samples seen
             self._facc = torch.zeros(2, 3, device=self.dev, dtype=torch.float64)
-        if self.interaction or self.field:
-            if template_faces is None or hand_faces is None or "faces" not in template_faces:
-                raise ValueError("Evaluator(interaction=True) / Evaluator(field=True) needs template_faces (faces, n_faces of "
-                                 "sdf_data.pack_templates) and hand_faces")
+        have_faces = template_faces is not None and hand_faces is not None and "faces" in template_faces
+        if (self.interaction or self.field or self.silhouette) and not have_faces:
+            raise ValueError("Evaluator(interaction=True) / Evaluator(field=True) / Evaluator(silhouette=True) needs template_faces "
+                             "(faces, n_faces of sdf_data.pack_templates) and hand_faces")
+        if have_faces:                                            # (also without a block: render.predicted_pair poses from them)
             self._tfaces = torch.as_tensor(template_faces["faces"]).to(self.dev, torch.int32)
             n = template_faces.get("n_faces")
             self._tn = torch.full((self._tfaces.shape[0],), self._tfaces.shape[1], dtype=torch.int32) if n is None else torch.as_tensor(n)
@@ -343,6 +364,8 @@ class Evaluator:
         self.total += B
         if self.interaction:
             self._feed_interaction(out, meta, obj_cls)
+        if self.silhouette:
+            self._feed_silhouette(out, tg, meta, obj_cls)
         if ho3d:                                                                  # main/test.py:133-176
             if cfg.use_inverse_kinematics:
                 joints, mesh = out["ik_joints_out"], out["ik_verts_out"]
@@ -386,16 +409,25 @@ class Evaluator:
     def interaction_per_sample(self, out, meta, obj_cls):
         """ops.eval_interaction on the predicted pair of every sample -> (its dict, used (B,) bool: obj_cls >= 0)"""
         from . import ops
-        dev = self.dev
-        root = meta["mano_root"].to(dev)
-        hand = (out["ik_verts_out"] if self.cfg.use_inverse_kinematics else out["mano_mesh_out"]).detach() + root[:, None]
-        cls = torch.as_tensor(obj_cls).to(dev).long()
-        used = cls >= 0
-        cls = cls.clamp_min(0)
-        rot, trans = out["obj_rot_out"].detach().mean(1), out["obj_trans_out"].detach().mean(1)
-        obj = self.templates[cls] @ batch_rodrigues(rot).transpose(1, 2) + (trans + meta["obj_center_cam"].to(dev))[:, None]
-        return ops.eval_interaction(hand, self._hfaces, obj, self._tfaces[cls], self._tn[cls], None, self.cfg.contact_dist,
-                                    self.cfg.interaction_voxel), used
+        from .render import predicted_pair
+        hand, hf, obj, of, on, used = predicted_pair(out, meta, obj_cls, self)
+        return ops.eval_interaction(hand, hf, obj, of, on, None, self.cfg.contact_dist, self.cfg.interaction_voxel), used
+
+    def silhouette_per_sample(self, out, targets, meta, obj_cls):
+        """the predicted pair rendered and counted against the mask targets -> (counts int32 (B, 4) = hand intersection, hand union,
+        object intersection, object union, used (B,) bool: obj_cls >= 0), on the device"""
+        from . import ops
+        from .render import predicted_pair, render_pair
+        pair = predicted_pair(out, meta, obj_cls, self)
+        masks = render_pair(pair, meta["cam_intr"], self.cfg, want=(), masks=True)
+        gh, go = targets["hand_seg"].to(self.dev), targets["obj_seg"].to(self.dev)
+        if gh.shape != masks["hand_seg"].shape or go.shape != masks["obj_seg"].shape:
+            raise ValueError(f"silhouette: mask targets {tuple(gh.shape)} / {tuple(go.shape)}, rendered {tuple(masks['hand_seg'].shape)}")
+        return ops.eval_silhouette(masks["hand_seg"], masks["obj_seg"], gh, go), pair[5]
+
+    def _feed_silhouette(self, out, targets, meta, obj_cls) -> None:
+        counts, used = self.silhouette_per_sample(out, targets, meta, obj_cls)
+        self._scounts.append(torch.cat([counts, used.to(torch.int32)[:, None]], 1))
 
     def _feed_interaction(self, out, meta, obj_cls) -> None:
         r, used = self.interaction_per_sample(out, meta, obj_cls)
@@ -462,6 +494,17 @@ class Evaluator:
                 print("Field:", file=f)
                 print("hand_chamfer=%.4f cm^2, obj_chamfer=%.4f cm^2, hand_left_out=%.3f, obj_left_out=%.3f"
                       % (hs / max(hn, 1.0) * 1.0e4, os_ / max(on, 1.0) * 1.0e4, 1.0 - hn / max(ht, 1.0), 1.0 - on / max(ot, 1.0)), file=f)
+        if self.silhouette:                                    # after everything else; integer counts from the device, fp64 division here
+            c = torch.cat(self._scounts).cpu().numpy().astype(np.float64) if self._scounts else np.zeros((0, 5))
+            line = []
+            for name, k in (("hand", 0), ("obj", 2)):
+                took = (c[:, 4] > 0) & (c[:, k + 1] > 0)
+                iou = float((c[took, k] / c[took, k + 1]).mean()) if took.any() else 0.0
+                line.append((name, iou, 1.0 - took.sum() / max(len(c), 1)))
+            with open(path, "a") as f:
+                print("Silhouette:", file=f)
+                print("hand_iou=%.6f, obj_iou=%.6f, hand_left_out=%.3f, obj_left_out=%.3f"
+                      % (line[0][1], line[1][1], line[0][2], line[1][2]), file=f)
         if self.ho3d:
             if self.native:
                 joints = list(torch.cat(self.joint_list).cpu().numpy()) if self.joint_list else []

@@ -2746,3 +2746,100 @@ def eval_surface(pred_verts, pred_n_verts, gt_verts, gt_faces, gt_n_faces=None, 
     if extras:
         out["samples"], out["nearest"] = samples, nearest
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Mesh rasteriser (csrc/raster.hip: hoisdf_raster_meshes, hoisdf_raster_overlay, hoisdf_eval_silhouette).  No gradient.
+# ---------------------------------------------------------------------------------------------
+def _raster_mesh(verts, faces, n_faces, B: Optional[int], what: str):
+    """-> (hoisdf_mesh or None, the tensors it points to, B, max_faces)"""
+    if verts is None:
+        return None, (), B, 0
+    verts = verts.contiguous().float()
+    _chk(verts)
+    if verts.dim() != 3 or verts.shape[2] != 3 or (B is not None and verts.shape[0] != B):
+        raise ValueError(f"raster_meshes: {what} vertices {tuple(verts.shape)}: one (V, 3) mesh per sample")
+    dev, B = verts.device, verts.shape[0]
+    f = faces.to(dev, torch.int32).contiguous()
+    n = None if n_faces is None else torch.as_tensor(n_faces).to(dev, torch.int32).contiguous()
+    if f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) or (n is not None and n.shape != (B,)):
+        raise ValueError(f"raster_meshes: {what} faces (F, 3) or (B, F, 3), counts (B,)")
+    F = f.shape[-2]
+    m = _lib.Mesh(verts=verts.data_ptr(), faces=f.data_ptr(), n_faces=None if n is None else n.data_ptr(),
+                  face_batch_stride=0 if f.dim() == 2 else 3 * F, V=verts.shape[1], max_faces=F)
+    return m, (verts, f, n), B, F
+
+
+@torch.no_grad()
+def raster_meshes(hand_verts, hand_faces, obj_verts, obj_faces, K, width: int, height: int, hand_n_faces=None, obj_n_faces=None,
+                  half_pixel: bool = False, near: float = 0.01, hm_shape=None, want=("ids", "depth", "counts"), out=None):
+    """hoisdf_raster_meshes: the hand mesh (B, Vh, 3) and the object mesh (B, Vo, 3), one camera frame, metres, faces (F, 3) shared
+    or (B, F, 3) with counts (B,), either mesh None; K (B, 6) or (B, 2, 3) = the top two rows of the camera matrix -> a dict with
+    what `want` names: ids int32 (B, height, width) (-1: background, else mesh << 16 | face row), depth float32 (0: background),
+    counts int32 (B, 2) = visible pixels per mesh and, with hm_shape = (hm_h, hm_w), hand_seg / obj_seg float32 (B, hm_h, hm_w):
+    the modal masks under the NEAREST fold of image_crop.  `out`: a dict of tensors to write into instead of new ones."""
+    if hand_verts is None and obj_verts is None:
+        raise ValueError("raster_meshes: one mesh at least")
+    mh, keep_h, B, Fh = _raster_mesh(hand_verts, hand_faces, hand_n_faces, None, "hand")
+    mo, keep_o, B, Fo = _raster_mesh(obj_verts, obj_faces, obj_n_faces, B, "object")
+    dev = (keep_h or keep_o)[0].device
+    K = K.to(dev).float().reshape(B, 6).contiguous()
+    _chk(K)
+    names = list(want) + (["hand_seg", "obj_seg"] if hm_shape is not None else [])
+    shapes = {"ids": ((B, int(height), int(width)), torch.int32), "depth": ((B, int(height), int(width)), torch.float32),
+              "counts": ((B, 2), torch.int32)}
+    if hm_shape is not None:
+        shapes["hand_seg"] = shapes["obj_seg"] = ((B, int(hm_shape[0]), int(hm_shape[1])), torch.float32)
+    res = {}
+    for k in names:
+        shape, dtype = shapes[k]
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"raster_meshes: out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        res[k] = t
+    nws = lib().hoisdf_raster_workspace_bytes(B, Fh, Fo)
+    if nws < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    hm_h, hm_w = (int(hm_shape[0]), int(hm_shape[1])) if hm_shape is not None else (0, 0)
+    call("hoisdf_raster_meshes", None if mh is None else C.addressof(mh), None if mo is None else C.addressof(mo), _p(K), B, int(width),
+         int(height), int(bool(half_pixel)), float(near), _p(res.get("ids")), _p(res.get("depth")), _p(res.get("hand_seg")),
+         _p(res.get("obj_seg")), hm_w, hm_h, _p(res.get("counts")), _p(ws), nws, _st())
+    return res
+
+
+@torch.no_grad()
+def raster_overlay(ids, image, colour=((70, 130, 255), (255, 160, 40)), alpha: int = 160, out=None):
+    """hoisdf_raster_overlay: ids int32 (B, H, W) of raster_meshes over image uint8 (B, H, W, 3) -> uint8 (B, H, W, 3): a covered pixel
+    is (alpha colour[mesh] + (256 - alpha) image + 128) >> 8 with colour = (hand rgb, object rgb), a background pixel is copied.
+    out may be `image` itself (in place)."""
+    ids = ids.contiguous()
+    image = image.contiguous()
+    if not ids.is_cuda or image.device != ids.device:
+        raise RuntimeError("hoisdf_amd ops need CUDA/HIP tensors on one device (no CPU fallback)")
+    if ids.dtype != torch.int32 or image.dtype != torch.uint8 or ids.dim() != 3 or tuple(image.shape) != tuple(ids.shape) + (3,):
+        raise ValueError(f"raster_overlay: ids int32 (B, H, W) {tuple(ids.shape)} and image uint8 (B, H, W, 3) {tuple(image.shape)}")
+    if out is None:
+        out = torch.empty_like(image)
+    elif out.shape != image.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != image.device:
+        raise ValueError("raster_overlay: out must be a contiguous uint8 tensor of the image's shape on its device")
+    col = (C.c_uint8 * 6)(*[int(c) for m in colour for c in m])
+    B, H, W = ids.shape
+    call("hoisdf_raster_overlay", _p(ids), _p(image), _p(out), C.addressof(col), int(alpha), B, W, H, _st())
+    return out
+
+
+@torch.no_grad()
+def eval_silhouette(pred_hand, pred_obj, gt_hand, gt_obj):
+    """hoisdf_eval_silhouette: four masks (B, ...) float32, set where > 0.5 -> int32 (B, 4): hand intersection, hand union, object
+    intersection, object union of predicted against ground truth (integer sums on the device)"""
+    B = pred_hand.shape[0]
+    masks = [m.reshape(B, -1).float().contiguous() for m in (pred_hand, pred_obj, gt_hand, gt_obj)]
+    _chk(*masks)
+    if any(m.shape != masks[0].shape for m in masks):
+        raise ValueError(f"eval_silhouette: four masks of one shape, got {[tuple(m.shape) for m in masks]}")
+    counts = torch.empty(B, 4, device=masks[0].device, dtype=torch.int32)
+    call("hoisdf_eval_silhouette", *[_p(m) for m in masks], B, masks[0].shape[1], _p(counts), _st())
+    return counts

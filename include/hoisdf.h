@@ -1248,6 +1248,67 @@ int hoisdf_eval_surface(const float* pred_verts, const int32_t* pred_n_verts, in
                         int n_samples, uint64_t seed, float* pred_to_gt, float* gt_to_pred, float* chamfer, int32_t* n_used,
                         float* samples_out, int32_t* nearest_out, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- raster: which pixels the posed hand mesh and the posed object mesh cover - ids, depth, modal masks, overlays, silhouette IoU ----
+ * reference: none - the reference reads its masks from per-frame image files and never renders a mesh.  csrc/raster.hip;
+ * hoisdf_amd/raster_oracle.py restates the rules below in numpy and reproduces every output bit for bit.  A z-buffered triangle
+ * rasteriser with exact integer coverage; no gradient, no shading, no anti-aliasing, no near-plane clipping.  The result does not
+ * depend on traversal order: two calls give the same bits.
+ * Every entry checks its arguments before any launch (HOISDF_ERR_INVALID, the argument named in hoisdf_last_error), returns 0
+ *   with nothing launched for B = 0 (B <= 65535), and only enqueues on `stream`.
+ *
+ * hoisdf_raster_meshes (2 launches: a setup pass over the faces, the raster pass over the pixels).
+ *   Inputs: hand, obj as hoisdf_mesh_sdf_rows takes them (n_faces clamped to 0 .. max_faces, face rows from there on never read),
+ *   ONE frame, metres, z forward.  Either mesh may be NULL, both NULL is invalid.  Mesh id: 0 = hand, 1 = obj.  K [B][6] floats =
+ *   the top two rows of the camera matrix (the skew and rotation terms of an augmented K' are honoured), the third row is taken
+ *   as 0 0 1.  width, height in 1 .. HOISDF_RASTER_MAX_SIZE.  half_pixel = 0: pixel (px, py) is sampled at (px, py), the OpenCV
+ *   convention of the labels; 1: at (px + 0.5, py + 0.5).  near: finite, > 0.
+ *   Projection, per vertex: floats widened to fp64, no product fused into a sum:  u = ((K0 x + K1 y) + K2 z) / z,
+ *   v = ((K3 x + K4 y) + K5 z) / z;  snapped to 1/256 pixel: X = rint(256 u), Y = rint(256 v), round half to even, as int32.
+ *   Skipped-face rule: a face takes no part in anything when it names a vertex outside 0 .. V-1; or a corner coordinate is not
+ *   finite; or a corner has z < near (NO clipping: a triangle that crosses the near plane is dropped whole); or a corner has
+ *   |u| or |v| >= 16384 (the guard band: |X|, |Y| <= 2^22); or its doubled area A2 = (X1-X0)(Y2-Y0) - (X2-X0)(Y1-Y0), in int64,
+ *   is 0.  No back-face culling (the hand is open at the wrist, templates need not be closed): a face with A2 < 0 has its
+ *   corners 1 and 2 swapped before the rules below.
+ *   Coverage, exact, in integers: the sample point of pixel (px, py) is (px', py') = (256 px + 128 half_pixel, 256 py + 128
+ *   half_pixel).  Edge i is the edge opposite corner i, from corner a = i + 1 to corner b = i + 2 (mod 3), dx = Xb - Xa,
+ *   dy = Yb - Ya; its edge function, an int64, is E = dx (py' - Ya) - dy (px' - Xa).  The pixel is covered when all three E > 0,
+ *   or when some are 0 and every such edge is a left edge (dy < 0: the interior at larger x along the pixel row) or a top edge
+ *   (dy = 0 and dx > 0: horizontal, the interior at larger y, y pointing down).  A sample point on an edge shared by two faces
+ *   belongs to exactly one of them, a point on a shared vertex to exactly one face of the fan.
+ *   Depth, perspective-correct, fp64, one order, nothing fused:  l_i = (double)E_i / (double)A2;
+ *   invz = (l0 (1/z0) + l1 (1/z1)) + l2 (1/z2);  z_pix = (float)(1 / invz).
+ *   Visibility: a pixel keeps the covering face with the smallest key (z_pix as float32, mesh id, face row), compared in that
+ *   order: an exact depth tie goes to the hand, within one mesh to the lower face row.
+ *   Outputs, all optional (NULL: skipped), one at least; every element of a given output is written:
+ *     id_out     int32 [B][height][width]: -1 for background, else mesh << 16 | face row
+ *     depth_out  float, same shape: z_pix, 0 for background
+ *     hand_seg, obj_seg  float [B][hm_h][hm_w], 1.0 / 0.0: mask pixel (i, j) reads raster pixel (floor((i + .5) width / hm_w),
+ *                floor((j + .5) height / hm_h)) - the NEAREST fold of hoisdf_image_crop, no full-size mask is written; they need
+ *                hm_w, hm_h >= 1, width % hm_w == 0 and height % hm_h == 0 (hm_w, hm_h are ignored without a mask).  The masks are
+ *                MODAL: a pixel where the object is in front is no hand pixel.
+ *     counts     int32 [B][2]: visible pixels per mesh at raster resolution (integer sums)
+ *   workspace: hoisdf_raster_workspace_bytes(B, hand max_faces, obj max_faces) device bytes (0 for a NULL mesh; -1 on an invalid
+ *   shape), 256-byte aligned: one 64-byte record per face row.
+ *   The raster pass is tile-major: a workgroup owns a HOISDF_RASTER_TILE x HOISDF_RASTER_TILE tile of one sample, each thread its
+ *   pixels outright, and the sample's records pass through LDS in chunks of HOISDF_RASTER_CHUNK.
+ * hoisdf_raster_overlay (1 launch): image_in, image_out u8 [B][height][width][3] on the device, id as id_out above; colour u8
+ *   [2][3] on the HOST (hand, obj; read before the call returns); alpha an integer in 0 .. 256.  A covered pixel becomes
+ *   (alpha colour[mesh][c] + (256 - alpha) in + 128) >> 8, a background pixel is copied.  image_out == image_in is allowed.
+ * hoisdf_eval_silhouette (1 launch): four masks float [B][n] (n in 1 .. 2^24), a value > 0.5 is set; counts int32 [B][4] = hand
+ *   intersection, hand union, object intersection, object union of predicted against ground truth.  Integer sums only: the IoU
+ *   is the caller's division. */
+#define HOISDF_RASTER_TILE 32
+#define HOISDF_RASTER_CHUNK 256
+#define HOISDF_RASTER_MAX_SIZE 4096
+long hoisdf_raster_workspace_bytes(int B, int hand_max_faces, int obj_max_faces);
+int hoisdf_raster_meshes(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const float* K, int B, int width, int height,
+                         int half_pixel, float near, int32_t* id_out, float* depth_out, float* hand_seg, float* obj_seg,
+                         int hm_w, int hm_h, int32_t* counts, void* workspace, long workspace_bytes, void* stream);
+int hoisdf_raster_overlay(const int32_t* id, const uint8_t* image_in, uint8_t* image_out, const uint8_t* colour, int alpha,
+                          int B, int width, int height, void* stream);
+int hoisdf_eval_silhouette(const float* pred_hand, const float* pred_obj, const float* gt_hand, const float* gt_obj, int B, int n,
+                           int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,12 @@ def parse_args():
     ap.add_argument("--field-surface", action="store_true",
                     help="also extract the zero level set of the two learned fields (Model.field_surface, hoisdf_iso_extract) and report "
                          "their Chamfer distance to the ground-truth meshes (cfg.eval_field); procedural MESHES as templates")
+    ap.add_argument("--silhouette", action="store_true",
+                    help="also report the IoU of the predicted hand's and object's rendered silhouettes against the mask targets "
+                         "(hoisdf_raster_meshes, cfg.eval_silhouette); procedural MESHES as templates")
+    ap.add_argument("--overlay", type=str, default="", metavar="DIR",
+                    help="write one image per sample into DIR: the predicted hand and object blended over the input crop "
+                         "(hoisdf_raster_overlay, cfg.overlay_dir; PNG where PIL imports, else binary PPM); procedural MESHES as templates")
     a = ap.parse_args()
     assert a.gpu_ids, "Please set propoer gpu ids"
     if "-" in a.gpu_ids:                                   # "0-3" -> "0,1,2,3" (main/test.py:66-70)
@@ -62,6 +68,8 @@ def main():
     cfg.native_metrics = bool(a.native_metrics)
     cfg.eval_interaction = bool(a.interaction)
     cfg.eval_field = bool(a.field_surface)
+    cfg.eval_silhouette = bool(a.silhouette)
+    cfg.overlay_dir = a.overlay or ""
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
     torch.cuda.set_device(dev)
@@ -75,7 +83,7 @@ def main():
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
     faces = None
-    if M.interaction_enabled(cfg) or M.field_enabled(cfg):   # point clouds have no inside and no surface: closed procedural meshes instead
+    if M.interaction_enabled(cfg) or M.field_enabled(cfg) or M.silhouette_enabled(cfg) or cfg.overlay_dir:   # point clouds have no inside and no surface: closed procedural meshes instead
         from hoisdf_amd.sdf_data import procedural_templates
         faces = procedural_templates(device=dev)
         templates = faces["verts"]
@@ -84,7 +92,11 @@ def main():
     for it, (inputs, targets, meta) in enumerate(loader):
         out = tester.predict(inputs, targets, meta, mano_layer=mano_layer)
         B = meta["mano_root"].shape[0]
-        ev.feed(out, targets, meta, (torch.arange(B) + it) % templates.shape[0])
+        obj_cls = (torch.arange(B) + it) % templates.shape[0]
+        ev.feed(out, targets, meta, obj_cls)
+        if cfg.overlay_dir:
+            from hoisdf_amd.render import write_overlays
+            write_overlays(cfg.overlay_dir, it * a.batch, inputs, out, meta, obj_cls, ev, cfg)
     out_dir = a.out_dir or (os.path.dirname(a.ckpt_path) if a.ckpt_path else "outputs/result")
     path = ev.write(out_dir)
     if ho3d:
