@@ -74,6 +74,16 @@ class Config:
     eval_interaction = False
     contact_dist = 0.005                 # metres: a hand vertex this close to the object (or inside it) is in contact
     interaction_voxel = 0.005            # metres: the cell of the intersection-volume grid (at most 64 cells per axis)
+    # not in the reference: training adds a hand-object interaction loss on the PREDICTED hand mesh and the PREDICTED object (the
+    # template posed by the mean rotation and translation votes): loss["interaction_rep"] = ObMan's repulsion of the vertices of
+    # either mesh that lie inside the other, loss["interaction_att"] = its saturating attraction of the hand's contact zones
+    # (vertices of the distal finger joints) onto the object (hoisdf_interaction_loss_fwd / _bwd, csrc/interact_loss.hip).  Also
+    # HOISDF_INTERACTION_LOSS=1.  Needs meta_info["obj_cls"]; not offered for the IK variant.  The two weights are UNTUNED starting
+    # values (no dataset and no trained weights here to tune them on); alpha is the length at which the attraction saturates
+    interaction_loss = False
+    interaction_rep_weight = 100.0
+    interaction_att_weight = 10.0
+    interaction_alpha = 0.01             # metres
     # not in the reference: the eval forward also extracts the zero level set of the two learned fields as triangle meshes
     # (Model.field_surface: hoisdf_iso_extract, csrc/isosurf.hip) and test.py's Evaluator reports their Chamfer distance to the
     # ground-truth MANO mesh and to the posed ground-truth template in a block appended to results.txt.  Also HOISDF_FIELD=1 /

@@ -35,7 +35,9 @@ LOSS_WEIGHTS = {  # main/train.py:115-127 <- cfg attribute
     "sdfhand_loss": "sdf_hand_weight", "sdfobj_loss": "sdf_obj_weight", "joint_heatmap": "hm_weight",
     "obj_seg": "obj_hm_weight", "hand_seg": "obj_hm_weight", "obj_rot": "obj_rot_weight",
     "obj_trans": "obj_trans_weight", "loss_joint_3d": "joint_weight", "loss_joint_cls": "cls_weight",
-    "loss_all_joint_3d": "joint_weight"}
+    "loss_all_joint_3d": "joint_weight",
+    # not in the reference: the hand-object interaction loss (cfg.interaction_loss)
+    "interaction_rep": "interaction_rep_weight", "interaction_att": "interaction_att_weight"}
 
 
 def _mix_seed(epoch_seed: int, draw: int) -> int:
@@ -297,12 +299,22 @@ class Trainer:
                     head = getattr(self.model, "mano_head", None)
                     src = MeshSdfSource(head.mano_layer if head is not None else self.model.ik_mano_layer, procedural_templates(), cfg)
                 self.seg_source = MeshSegSource(src, cfg)
+        self.interaction_source = None
+        if self.model.interaction_loss_enabled():       # cfg.interaction_loss / HOISDF_INTERACTION_LOSS=1: the meshes of the existing source, else the same stand-ins
+            src = self.sdf_source if self.sdf_source is not None else getattr(self.seg_source, "source", None)
+            if src is None:
+                from .sdf_data import MeshSdfSource, procedural_templates
+                src = MeshSdfSource(self.model.mano_head.mano_layer, procedural_templates(), cfg)
+            self.interaction_source = src
+            self.model.set_interaction_source(src)
         if dataset is None and sdf_store is not None:
             dataset = SyntheticSdfDataset(cfg, sdf_store.n_frames, seed=self.rank)
         elif dataset is None and self.sdf_source is not None:
             dataset = SyntheticMeshSdfDataset(cfg, self.sdf_source.n_templates, seed=self.rank)
         elif dataset is None and self.seg_source is not None:      # the full synthetic sample + the template its masks are rendered from
             dataset = SyntheticMeshSdfDataset(cfg, self.seg_source.n_templates, seed=self.rank, keep_points=True)
+        elif dataset is None and self.interaction_source is not None:   # likewise: the template the predicted object is posed from
+            dataset = SyntheticMeshSdfDataset(cfg, self.interaction_source.n_templates, seed=self.rank, keep_points=True)
         ds = dataset if dataset is not None else SyntheticDataset(cfg, seed=self.rank)
         bs = batch_size or cfg.train_batch_size
         sampler = torch.utils.data.distributed.DistributedSampler(ds, self.world, self.rank, shuffle=True) \

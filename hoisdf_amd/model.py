@@ -162,9 +162,50 @@ class Model(nn.Module):
         # the IK variant owns no MANO layer (its state_dict has no mano_head.*): the layer its native post-process solves with is a
         # plain attribute, NOT a registered submodule (the checkpoint schema stays as it is)
         self.set_ik_mano_layer(mano_layer if cfg.use_inverse_kinematics else None)
+        self.set_interaction_source(None)
+        if cfg.use_inverse_kinematics and self.interaction_loss_enabled():
+            raise ValueError("cfg.interaction_loss needs the predicted hand mesh in training: the IK variant (cfg.use_inverse_kinematics) has none")
 
     def set_ik_mano_layer(self, mano_layer):
         object.__setattr__(self, "ik_mano_layer", mano_layer)
+
+    def interaction_loss_enabled(self) -> bool:
+        """cfg.interaction_loss (default False) or HOISDF_INTERACTION_LOSS=1: training adds interaction_rep / interaction_att"""
+        return bool(getattr(self.cfg, "interaction_loss", False)) or os.environ.get("HOISDF_INTERACTION_LOSS", "") == "1"
+
+    def set_interaction_source(self, source, att_w_hand=None, rep_w_hand=None, rep_w_obj=None):
+        """the meshes of the interaction loss: a ``sdf_data.MeshSdfSource`` (object templates + the MANO layer's faces; the Trainer
+        hands its own over) and the per-vertex weights - ``att_w_hand`` (778,) defaults to sdf_data.contact_zone_weights of the
+        source's layer, the two repulsion weights to ones.  A plain attribute, no submodule: the checkpoint schema stays as it is"""
+        if source is not None and att_w_hand is None:
+            from .sdf_data import contact_zone_weights
+            att_w_hand = contact_zone_weights(source.layer.th_weights)
+        object.__setattr__(self, "_interaction", None if source is None else (source, att_w_hand, rep_w_hand, rep_w_obj))
+
+    def _interaction_losses(self, hand_rel, obj_rot, obj_trans, meta_info, loss):
+        """The predicted hand against the predicted object (hoisdf_interaction_loss_fwd / _bwd): loss["interaction_rep"] = the
+        repulsion of both directions, loss["interaction_att"] = the attraction of the hand's contact zones, each (B,).  The object
+        is posed in torch from the mean votes, so autograd carries the vertex gradient on to both vote heads; a sample without an
+        evaluated object (obj_cls < 0) has face and vertex count 0 and adds 0."""
+        if self._interaction is None:
+            raise RuntimeError("cfg.interaction_loss needs the meshes: Model.set_interaction_source(MeshSdfSource) (the Trainer does it)")
+        if "obj_cls" not in meta_info:
+            raise KeyError("cfg.interaction_loss needs meta_info['obj_cls']: the object template of every sample (-1: none)")
+        from .metrics import batch_rodrigues
+        src, att_w, rep_wh, rep_wo = self._interaction
+        dev = hand_rel.device
+        tm = src.to(dev).templates
+        cls = meta_info["obj_cls"].to(dev).long().view(-1)
+        used, k = cls >= 0, cls.clamp_min(0)
+        hand = hand_rel + meta_info["mano_root"][:, None]
+        R = batch_rodrigues(obj_rot[-1].mean(1))
+        obj = tm["verts"][k] @ R.transpose(1, 2) + (obj_trans[-1].mean(1) + meta_info["obj_center_cam"])[:, None]
+        zero = torch.zeros_like(tm["n_faces"][k])
+        rep_hand, att, rep_obj = ops.interaction_loss(
+            hand, src.layer.th_faces, obj, tm["faces"][k], torch.where(used, tm["n_faces"][k], zero), torch.where(used, tm["n_verts"][k], zero),
+            rep_wh, att_w, rep_wo, float(self.cfg.interaction_alpha))
+        loss["interaction_rep"] = rep_hand + rep_obj
+        loss["interaction_att"] = att
 
     def _ik_layer(self, device):
         """the IK solve's layer on ``device``: as no submodule it does not follow Model.to, so the first native call moves it (once)"""
@@ -549,6 +590,8 @@ class Model(nn.Module):
             obj_rot, obj_trans = self._object_stack(obj)
         with plan.on_side():                            # ---- under the big vote-head GEMMs of the ambient stream
             self._mano_and_object_pose(hs, obj_rot, obj_trans, targets, training, loss, out)
+            if training and self.interaction_loss_enabled():
+                self._interaction_losses(out["mano_mesh_out"], obj_rot, obj_trans, meta_info, loss)
             side_made = [t for t in list(loss.values()) + list(out.values()) if torch.is_tensor(t)]
         self._hand_votes(hand_rel, hand_enc, targets, training, loss, out)             # ---- (ambient stream)
         plan.join(*side_made)

@@ -2632,6 +2632,80 @@ def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=N
 
 
 # ---------------------------------------------------------------------------------------------
+# Hand-object interaction loss (csrc/interact_loss.hip, hoisdf_interaction_loss_fwd / _bwd): repulsion and attraction with gradients
+# to both vertex arrays.
+# ---------------------------------------------------------------------------------------------
+def _loss_weight(w, B: int, V: int, dev, what: str):
+    """a per-vertex weight array -> (tensor or None, batch stride in elements): (V,) shared by the batch, (B, V) per sample"""
+    if w is None:
+        return None, 0
+    w = torch.as_tensor(w).detach().to(dev, torch.float32).contiguous()
+    if w.shape not in ((V,), (B, V)):
+        raise ValueError(f"interaction_loss: {what} {tuple(w.shape)}: ({V},) or ({B}, {V})")
+    return w, (0 if w.dim() == 1 else V)
+
+
+class _InteractionLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hand_verts, obj_verts, hf, of, hn, on, ov, weights, alpha):
+        hv, obv = hand_verts.detach().contiguous().float(), obj_verts.detach().contiguous().float()
+        _chk(hv, obv)
+        dev, B = hv.device, hv.shape[0]
+        Vh, Vo, Fh, Fo = hv.shape[1], obv.shape[1], hf.shape[-2], of.shape[-2]
+        mh = _lib.Mesh(verts=hv.data_ptr(), faces=hf.data_ptr(), n_faces=None if hn is None else hn.data_ptr(),
+                       face_batch_stride=0 if hf.dim() == 2 else 3 * Fh, V=Vh, max_faces=Fh)
+        mo = _lib.Mesh(verts=obv.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
+                       face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=Vo, max_faces=Fo)
+        nws = lib().hoisdf_interaction_loss_workspace_bytes(B, Vh, Fh, Vo, Fo)
+        if nws < 0:
+            raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+        ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+        out = [torch.empty(B, device=dev, dtype=torch.float32) for _ in range(3)]
+        (wr, sr), (wa, sa), (wo, so) = weights
+        common = (C.addressof(mh), C.addressof(mo), _p(ov), B, _p(wr), sr, _p(wa), sa, _p(wo), so, float(alpha))
+        call("hoisdf_interaction_loss_fwd", *common, _p(out[0]), _p(out[1]), _p(out[2]), _p(ws), nws, _st())
+        # the backward reads the workspace and every input again: all of them stay alive, and unchanged, with the context
+        ctx.keep = (hv, obv, hf, of, hn, on, ov, wr, wa, wo, mh, mo, ws)
+        ctx.common, ctx.nws = common, nws
+        ctx.set_materialize_grads(False)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, g_rep_hand, g_att, g_rep_obj):
+        hv, obv = ctx.keep[0], ctx.keep[1]
+        gs = [None if g is None else g.contiguous().float() for g in (g_rep_hand, g_att, g_rep_obj)]
+        _chk(*gs)
+        d_hand, d_obj = torch.empty_like(hv), torch.empty_like(obv)
+        call("hoisdf_interaction_loss_bwd", *ctx.common, _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(d_hand), _p(d_obj), _p(ctx.keep[-1]), ctx.nws, _st())
+        return d_hand, d_obj, None, None, None, None, None, None, None
+
+
+def interaction_loss(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=None, obj_n_verts=None, rep_w_hand=None,
+                     att_w_hand=None, rep_w_obj=None, alpha: float = 0.01, hand_n_faces=None):
+    """hoisdf_interaction_loss_fwd / _bwd: the meshes as ``eval_interaction`` takes them (one frame, metres); rep_w_hand, att_w_hand
+    (Vh,) or (B, Vh) and rep_w_obj (Vo,) or (B, Vo) per-vertex weights, None = ones; alpha: the length at which the attraction
+    saturates -> (rep_hand, att, rep_obj), each (B,): the weighted means of max(0, -sdf_obj) and alpha tanh(max(0, sdf_obj) / alpha)
+    over the hand vertices and of max(0, -sdf_hand) over the object's vertices that count.  Gradients flow to hand_verts and obj_verts
+    only (the envelope rule of include/hoisdf.h "interaction loss"); order-fixed: two calls give the same bits."""
+    if hand_verts.dim() != 3 or obj_verts.dim() != 3 or obj_verts.shape[0] != hand_verts.shape[0] or hand_verts.shape[2] != 3 or obj_verts.shape[2] != 3:
+        raise ValueError(f"interaction_loss: hand {tuple(hand_verts.shape)} and object {tuple(obj_verts.shape)}: one (V, 3) mesh of each per sample")
+    _chk(hand_verts, obj_verts)
+    dev, B = hand_verts.device, hand_verts.shape[0]
+    hf = hand_faces.to(dev, torch.int32).contiguous()
+    of = obj_faces.to(dev, torch.int32).contiguous()
+    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
+    ov = None if obj_n_verts is None else torch.as_tensor(obj_n_verts).to(dev, torch.int32).contiguous()
+    hn = None if hand_n_faces is None else torch.as_tensor(hand_n_faces).to(dev, torch.int32).contiguous()
+    if any(f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) for f in (hf, of)) or any(
+            n is not None and n.shape != (B,) for n in (on, ov, hn)):
+        raise ValueError("interaction_loss: faces (F, 3) or (B, F, 3), counts (B,)")
+    Vh, Vo = hand_verts.shape[1], obj_verts.shape[1]
+    weights = (_loss_weight(rep_w_hand, B, Vh, dev, "rep_w_hand"), _loss_weight(att_w_hand, B, Vh, dev, "att_w_hand"),
+               _loss_weight(rep_w_obj, B, Vo, dev, "rep_w_obj"))
+    return _InteractionLoss.apply(hand_verts, obj_verts, hf, of, hn, on, ov, weights, float(alpha))
+
+
+# ---------------------------------------------------------------------------------------------
 # Surface from a sampled field (csrc/isosurf.hip, the hoisdf_iso_* entries and hoisdf_eval_surface).  No gradient.
 # ---------------------------------------------------------------------------------------------
 def _iso_grid(grid, n: int):

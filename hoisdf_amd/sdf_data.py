@@ -191,6 +191,17 @@ def pack_templates(meshes, scale: float = 1.0, device="cpu") -> Dict[str, torch.
     return {"verts": torch.from_numpy(verts).to(device), "faces": torch.from_numpy(faces).to(device), "n_faces": torch.from_numpy(n).to(device)}
 
 
+DISTAL_JOINTS = (3, 6, 9, 12, 15)                              # of MANO's 16: the last joint of each of the five fingers
+
+
+def contact_zone_weights(skin_weights: torch.Tensor) -> torch.Tensor:
+    """(V, 16) skinning weights -> (V,) float32: 1 on the vertices that a distal finger joint moves most (the finger tips and pads),
+    else 0.  The attraction zones of the interaction loss; ObMan's own zone files are not redistributable, this is derived from the
+    layer alone."""
+    top = skin_weights.detach().argmax(1)
+    return torch.isin(top, torch.tensor(DISTAL_JOINTS, device=top.device)).float()
+
+
 class MeshSdfSource:
     """The SDF query points of a training batch computed on the device from the batch's own meshes (hoisdf_mesh_sdf_rows) instead of
     read from precomputed ``sdf_processed`` rows: per sample ``cfg.mesh_sdf_candidates`` x (num_samp_hand + num_samp_obj) candidate
@@ -210,17 +221,26 @@ class MeshSdfSource:
             vert_label = torch.from_numpy(vertex_part_labels(mano_layer.th_weights.detach().cpu().numpy()))
         self.vert_label = torch.as_tensor(vert_label).to(torch.int32)
         self.n_templates = self.templates["verts"].shape[0]
+        # the vertex rows of a template that its faces name (the rows behind them repeat vertex 0: padding)
+        f, n = self.templates["faces"].long(), self.templates["n_faces"].long()
+        named = torch.where(torch.arange(f.shape[1], device=f.device)[None, :, None] < n[:, None, None], f, torch.zeros_like(f))
+        self.templates["n_verts"] = (named.flatten(1).max(1).values + 1).to(torch.int32) * (n > 0).to(torch.int32)
+
+    def to(self, dev):
+        """the layer, the templates and the labels on ``dev`` (moved once)"""
+        if next(self.layer.buffers()).device != dev:
+            self.layer.to(dev)
+        if self.templates["verts"].device != dev:
+            self.templates = {k: v.to(dev) for k, v in self.templates.items()}
+            self.vert_label = self.vert_label.to(dev)
+        return self
 
     def meshes(self, targets, meta):
         """-> hand verts (B, 778, 3), hand faces (F, 3), object verts (B, V, 3), object faces (B, F, 3), object face counts (B,):
         camera metres, on the device of ``targets["mano_param"]``"""
         from .metrics import batch_rodrigues
         dev = targets["mano_param"].device
-        if next(self.layer.buffers()).device != dev:
-            self.layer.to(dev)
-        if self.templates["verts"].device != dev:
-            self.templates = {k: v.to(dev) for k, v in self.templates.items()}
-            self.vert_label = self.vert_label.to(dev)
+        self.to(dev)
         assets = self.layer.kernel_assets()
         if assets is None:
             raise RuntimeError("MeshSdfSource needs the MANO layer the HIP head takes (on the GPU, wrist-centred, flat hand mean)")

@@ -1181,6 +1181,55 @@ int hoisdf_eval_interaction(const hoisdf_mesh* hand, const hoisdf_mesh* obj, con
                             float* volume, int32_t* inside_count, uint8_t* inside_out, float* grid_out,
                             void* workspace, long workspace_bytes, void* stream);
 
+/* ---- interaction loss: the same quantities in a form to train against - repulsion and attraction, with their gradients ------------
+ * reference: none - the reference trains every part against ground truth and never couples the hand to the object.  ObMan (Hasson
+ * et al., CVPR 2019) trains with a repulsion of the vertices that lie inside the other mesh and a saturating attraction of contact
+ * zones onto the surface; these are those two terms on hoisdf_mesh_sdf's exact distance.  csrc/interact_loss.hip;
+ * hoisdf_amd/interaction_loss_oracle.py restates it in numpy.  Both meshes as hoisdf_eval_interaction takes them, in ONE frame,
+ * lengths in metres; obj_n_verts as there (padding object vertices take no part and, as query points, get no gradient).  A mesh whose
+ * face count is 0 is absent: its vertices are no query points either, so such a sample gives three zeros and zero gradients.
+ * Weights, each may be NULL = all ones: rep_w_hand, att_w_hand [hand V] and rep_w_obj [obj V] floats per sample, with a batch stride
+ *   in elements of 0 (one array shared by the batch) or V.  alpha > 0: the length at which the attraction saturates.
+ * Checked before the first launch by both entries (HOISDF_ERR_INVALID, the argument named in hoisdf_last_error): hand, obj, verts,
+ *   faces, an output or the workspace null; B < 0 or B > 65535; a mesh without vertices; max_faces > HOISDF_MESH_MAX_FACES; a
+ *   face_batch_stride that is neither 0 nor >= 3 max_faces; a weight stride that is neither 0 nor V; alpha <= 0 or not finite; a
+ *   workspace below hoisdf_interaction_loss_workspace_bytes(B, hand V, hand max_faces, obj V, obj max_faces) device bytes (-1 on an
+ *   invalid shape; 256-byte aligned).  B = 0 returns 0 with nothing launched.  Both only enqueue on `stream`.
+ * hoisdf_interaction_loss_fwd (5 launches: hoisdf_mesh_prepare x 2, hoisdf_mesh_sdf x 2, the per-sample reduction).  With sdf_obj(v)
+ *   of hand vertex v to the object mesh and sdf_hand(v) of object vertex v to the hand mesh - hoisdf_mesh_sdf's distance, tie rule
+ *   and sign rule - per sample, all [B]:
+ *     rep_hand = sum_v rep_w_hand[v] max(0, -sdf_obj(v)) / sum_v rep_w_hand[v]                      over the hand vertices
+ *     att      = sum_v att_w_hand[v] alpha tanh(max(0, sdf_obj(v)) / alpha) / sum_v att_w_hand[v]   over the hand vertices
+ *     rep_obj  = sum_v rep_w_obj[v] max(0, -sdf_hand(v)) / sum_v rep_w_obj[v]                       over v < obj_n_verts[b]
+ *   The denominators do not depend on the geometry; one that is not positive gives 0.  A query point whose mesh has no usable face
+ *   (distance 3e38) adds 0 to every numerator.  Sums in fp64: thread t of 256 takes vertices t, t + 256, ... in ascending order, the
+ *   256 partial sums meet in the fixed tree s[t] += s[t + 128], s[t + 64], ... ; one rounding to fp32.
+ *   The workspace keeps sdf, winning face and barycentric weights of every query point of both directions, the prepared meshes and
+ *   the denominators: hoisdf_interaction_loss_bwd reads them, so between the two calls the workspace, both vertex arrays, the
+ *   faces, the counts, the weights and alpha stay as they were.
+ * hoisdf_interaction_loss_bwd (2 launches, one per destination mesh): upstream gradients g_rep_hand, g_att, g_rep_obj [B] (any may
+ *   be NULL = zero) -> d_hand_verts [B][hand V][3], d_obj_verts [B][obj V][3]; every row is written, a padding row gets 0.
+ *   Rule: with c = sum_k beta_k x_k the closest point on the winning face of query point p, d = |p - c|, n = (p - c) / d and the sign
+ *   s held piecewise constant, d sdf / d p = s n and d sdf / d x_k = -beta_k s n (the envelope rule: face, edge and corner regions
+ *   alike).  coef(p) = the derivative of p's terms by sdf - -1 for the repulsion where sdf < 0, 1 - tanh^2(sdf / alpha) for the
+ *   attraction where sdf > 0 - times the weight, divided by the denominator, times the upstream gradient.  A vertex receives
+ *   (1) its own term coef s n as a query point and (2) -beta_k coef s n of every query point of the OTHER mesh whose winning face
+ *   names it as corner k.  A point with d = 0, without a usable face or past obj_n_verts contributes nothing.
+ *   Order: no atomics; each destination vertex is owned by one lane, which adds in fp64 its own term first, then the other mesh's
+ *   query points in ASCENDING query index (staged through LDS in tiles of HOISDF_INTERACT_LOSS_TILE records), corners 0, 1, 2 within
+ *   a record, and rounds to fp32 once.  Two calls give the same bits; a batch equals its samples run one by one, bit for bit. */
+#define HOISDF_INTERACT_LOSS_TILE 64
+long hoisdf_interaction_loss_workspace_bytes(int B, int hand_V, int hand_max_faces, int obj_V, int obj_max_faces);
+int hoisdf_interaction_loss_fwd(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, int B,
+                                const float* rep_w_hand, long rep_w_hand_stride, const float* att_w_hand, long att_w_hand_stride,
+                                const float* rep_w_obj, long rep_w_obj_stride, float alpha,
+                                float* rep_hand, float* att, float* rep_obj, void* workspace, long workspace_bytes, void* stream);
+int hoisdf_interaction_loss_bwd(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, int B,
+                                const float* rep_w_hand, long rep_w_hand_stride, const float* att_w_hand, long att_w_hand_stride,
+                                const float* rep_w_obj, long rep_w_obj_stride, float alpha,
+                                const float* g_rep_hand, const float* g_att, const float* g_rep_obj,
+                                float* d_hand_verts, float* d_obj_verts, const void* workspace, long workspace_bytes, void* stream);
+
 /* ---- iso-surface: a sampled field as an indexed triangle mesh, and its Chamfer distance to a ground-truth mesh -------------------
  * reference: none - the reference reads its two fields only at the points sdf_infer ranks.  AlignSDF and gSDF, which its field
  * code descends from, report the Chamfer distance of the extracted zero level set.  csrc/isosurf.hip;
