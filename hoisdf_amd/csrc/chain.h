@@ -1,6 +1,6 @@
-// Helpers shared by the host-side chains of the coarse entries (layers.hip, sdf_query.hip): a bump allocator over caller buffers
-// (with a null base it only measures - the size queries run the same carving code as the real calls) and the linear-layer
-// dispatch of the library defaults (fp32 emulated on the bf16 pipe from 2048 rows up, otherwise the exact-f32 kernels).
+// Helpers shared by the host-side chains of the coarse entries (layers.hip, sdf_query.hip): the linear-layer dispatch of the
+// library defaults (fp32 emulated on the bf16 pipe from 2048 rows up, otherwise the exact-f32 kernels), its scratch taken from
+// the Bump of common.h (with a null base it only measures - the size queries run the same carving code as the real calls).
 #pragma once
 #include <stdlib.h>
 
@@ -16,21 +16,6 @@ constexpr long EMU_MIN_ROWS = 2048;      // below: a handful of tiles, latency-b
 constexpr long EMU_DW_MIN_ROWS = 8192;   // grad-weight contracts over the rows: >= 32 slabs per slice at 256 slices
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// bump allocator over a caller buffer; with base == nullptr it only measures
-struct Bump {
-  char* base; long cap; long off = 0; bool overflow = false;
-  Bump(void* b, long c) : base(static_cast<char*>(b)), cap(c) {}
-  void* take(long bytes) {
-    off = (off + 255) & ~255L;
-    const long at = off;
-    off += bytes;
-    if (!base) return nullptr;
-    if (off > cap) { overflow = true; return nullptr; }
-    return base + at;
-  }
-  float* floats(long n) { return static_cast<float*>(take(n * 4)); }
-};
 
 // Whether a forward call left row magnitudes in its saved block depends on process-wide switches (hoisdf_set_gemm_emu, the form): the
 // forward RECORDS what it did per block (keyed by the address of the block's magnitude region) and the backward of that block asks

@@ -22,6 +22,24 @@ int check_launch(const char* what);
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// bump allocator over a caller buffer, every piece 256-byte aligned; with base == nullptr it only measures, so a size query and
+// the call it sizes run the same carving code
+struct Bump {
+  char* base; long cap; long off = 0; bool overflow = false;
+  Bump(void* b, long c) : base(static_cast<char*>(b)), cap(c) {}
+  void* take(long bytes) {
+    off = (off + 255) & ~255L;
+    const long at = off;
+    off += bytes;
+    if (!base) return nullptr;
+    if (off > cap) { overflow = true; return nullptr; }
+    return base + at;
+  }
+  float* floats(long n) { return static_cast<float*>(take(n * 4)); }
+  int32_t* ints(long n) { return static_cast<int32_t*>(take(n * 4)); }
+  long bytes() const { return (off + 255) & ~255L; }     // what was taken, as a whole number of 256-byte pieces
+};
+
 // ---- counter-based RNG for dropout ----------------------------------------------------
 // keep(row, col) is a pure function of (seed, row, col) so the backward pass regenerates the mask:
 //     x = mix(seed) + row * G1 + col * G2          (two Weyl sequences, odd 32-bit constants)

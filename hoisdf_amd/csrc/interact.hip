@@ -189,8 +189,16 @@ __global__ __launch_bounds__(256) void interact_reduce_kernel(const InteractRedu
   }
 }
 
-static long interact_workspace_bytes(long B, long Vh, long Fh, long Vo, long Fo) {
-  return mesh_buffers_bytes(B, Fh) + mesh_buffers_bytes(B, Fo) + align256(B * Vh * 4) + align256(B * Vo * 4) + align256(B * IG_BLOCKS * 4);
+// ---- workspace: both prepared meshes, the two vertex distance arrays, the voxel pass's block counts ------------------------------------
+struct InteractWorkspace { MeshPair m; float *sdf_ho, *sdf_oh; int32_t* partial; };
+
+static InteractWorkspace interact_workspace(Bump& w, long B, long Vh, long Fh, long Vo, long Fo) {
+  InteractWorkspace s;
+  s.m = mesh_pair(w, B, Fh, Fo);
+  s.sdf_ho = w.floats(B * Vh);
+  s.sdf_oh = w.floats(B * Vo);
+  s.partial = w.ints(B * IG_BLOCKS);
+  return s;
 }
 
 }  // namespace hoisdf
@@ -201,56 +209,36 @@ extern "C" long hoisdf_eval_interaction_workspace_bytes(int B, int hand_V, int h
   if (!mesh_shape_ok("eval_interaction_workspace_bytes (hand)", B, hand_V, hand_max_faces) ||
       !mesh_shape_ok("eval_interaction_workspace_bytes (obj)", B, obj_V, obj_max_faces))
     return -1;
-  return interact_workspace_bytes(B, hand_V, hand_max_faces, obj_V, obj_max_faces);
+  Bump w(nullptr, 0);
+  interact_workspace(w, B, hand_V, hand_max_faces, obj_V, obj_max_faces);
+  return w.bytes();
 }
 
 extern "C" int hoisdf_eval_interaction(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, int B,
                                        float contact_dist, float voxel, float* pen_hand, float* pen_obj, float* min_dist,
                                        int32_t* contact_verts, int32_t* in_contact, float* volume, int32_t* inside_count,
                                        uint8_t* inside_out, float* grid_out, void* workspace, long workspace_bytes, void* stream) {
-  HOISDF_REQUIRE(hand && obj, HOISDF_ERR_INVALID, "eval_interaction: null pointer (hand, obj)");
-  if (!mesh_shape_ok("eval_interaction (hand)", B, hand->V, hand->max_faces) || !mesh_shape_ok("eval_interaction (obj)", B, obj->V, obj->max_faces))
-    return HOISDF_ERR_INVALID;
+  if (!mesh_desc_ok("eval_interaction", "hand", hand, B) || !mesh_desc_ok("eval_interaction", "obj", obj, B)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(contact_dist >= 0.f && contact_dist <= 3.0e38f, HOISDF_ERR_INVALID, "eval_interaction: contact_dist=%g (>= 0, finite)",
                  (double)contact_dist);
   HOISDF_REQUIRE(voxel > 0.f && voxel <= 3.0e38f, HOISDF_ERR_INVALID, "eval_interaction: voxel=%g (> 0, finite)", (double)voxel);
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->face_batch_stride == 0 || m->face_batch_stride >= 3L * m->max_faces, HOISDF_ERR_INVALID,
-                   "eval_interaction: face_batch_stride=%ld (0 or >= 3 max_faces)", m->face_batch_stride);
   if (B == 0) return HOISDF_OK;
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->V > 0 && m->verts && (m->max_faces == 0 || m->faces), HOISDF_ERR_INVALID,
-                   "eval_interaction: null pointer (verts, faces) or a mesh without vertices");
+  if (!mesh_data_ok("eval_interaction", "hand", hand) || !mesh_data_ok("eval_interaction", "obj", obj)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(pen_hand && pen_obj && min_dist && contact_verts && in_contact && volume && inside_count, HOISDF_ERR_INVALID,
                  "eval_interaction: null pointer (pen_hand, pen_obj, min_dist, contact_verts, in_contact, volume, inside_count)");
   HOISDF_REQUIRE(workspace, HOISDF_ERR_INVALID, "eval_interaction: null pointer (workspace)");
-  const long need = interact_workspace_bytes(B, hand->V, hand->max_faces, obj->V, obj->max_faces);
-  HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "eval_interaction: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  Bump w(workspace, workspace_bytes);
+  const InteractWorkspace s = interact_workspace(w, B, hand->V, hand->max_faces, obj->V, obj->max_faces);
+  HOISDF_REQUIRE(workspace_bytes >= w.bytes(), HOISDF_ERR_INVALID, "eval_interaction: workspace of %ld bytes, %ld needed", workspace_bytes,
+                 w.bytes());
   hipStream_t st = as_stream(stream);
-  char* w = (char*)workspace;
-  const MeshBuffers mh = carve(w, B, hand->max_faces);
-  w += mesh_buffers_bytes(B, hand->max_faces);
-  const MeshBuffers mo = carve(w, B, obj->max_faces);
-  w += mesh_buffers_bytes(B, obj->max_faces);
-  float* sdf_ho = (float*)w;
-  w += align256((long)B * hand->V * 4);
-  float* sdf_oh = (float*)w;
-  w += align256((long)B * obj->V * 4);
-  int32_t* partial = (int32_t*)w;
-  launch_prepare(hand->verts, B, hand->V, hand->faces, hand->face_batch_stride, hand->n_faces, hand->max_faces, mh, st);
-  launch_prepare(obj->verts, B, obj->V, obj->faces, obj->face_batch_stride, obj->n_faces, obj->max_faces, mo, st);
-  // every hand vertex against the object, every object vertex (padding rows too: they are left out in the reduction) against the hand
-  MeshSdfArgs ho = {hand->verts, 3, mo.tris, mo.box, obj->n_faces, obj->max_faces, hand->V, sdf_ho, 1, nullptr, nullptr, nullptr,
-                    nullptr, 0, nullptr, nullptr, 0.f, 0};
-  launch_sdf(ho, B, st);
-  MeshSdfArgs oh = {obj->verts, 3, mh.tris, mh.box, hand->n_faces, hand->max_faces, obj->V, sdf_oh, 1, nullptr, nullptr, nullptr,
-                    nullptr, 0, nullptr, nullptr, 0.f, 0};
-  launch_sdf(oh, B, st);
-  InteractVoxelArgs va = {mh.tris, mh.box, hand->n_faces, hand->max_faces, mo.tris, mo.box, obj->n_faces, obj->max_faces, voxel, partial,
-                          inside_out};
+  launch_both_ways(*hand, *obj, B, s.m, {s.sdf_ho, nullptr, nullptr}, {s.sdf_oh, nullptr, nullptr}, st);
+  InteractVoxelArgs va = {s.m.hand.tris, s.m.hand.box, hand->n_faces, hand->max_faces, s.m.obj.tris, s.m.obj.box, obj->n_faces,
+                          obj->max_faces, voxel, s.partial, inside_out};
   hipLaunchKernelGGL(interact_voxel_kernel, dim3(IG_BLOCKS, B), dim3(256), 0, st, va);
-  InteractReduceArgs ra = {sdf_ho, hand->V, sdf_oh, obj->V, obj_n_verts, mh.box, mo.box, voxel, contact_dist, partial,
+  InteractReduceArgs ra = {s.sdf_ho, hand->V, s.sdf_oh, obj->V, obj_n_verts, s.m.hand.box, s.m.obj.box, voxel, contact_dist, s.partial,
                            pen_hand, pen_obj, min_dist, volume, grid_out, contact_verts, in_contact, inside_count};
   hipLaunchKernelGGL(interact_reduce_kernel, dim3(B), dim3(256), 0, st, ra);
   return check_launch("eval_interaction");
 }
+

@@ -191,57 +191,51 @@ __global__ __launch_bounds__(IL_TILE) void interact_loss_bwd_kernel(const LossBw
 }
 
 // ---- workspace: both prepared meshes, then per direction sdf / face / bary, then the denominators -----------------------------------
-struct LossWorkspace { MeshBuffers mh, mo; float *sdf_ho, *bary_ho, *sdf_oh, *bary_oh; int32_t *face_ho, *face_oh; double* den; };
+// The forward writes it and the backward reads it: one layout function for both and for the size query.
+struct LossWorkspace { MeshPair m; VertexSdf ho, oh; double* den; };
 
-static long loss_workspace_bytes(long B, long Vh, long Fh, long Vo, long Fo) {
-  return mesh_buffers_bytes(B, Fh) + mesh_buffers_bytes(B, Fo) + 2 * align256(B * Vh * 4) + align256(B * Vh * 12) + 2 * align256(B * Vo * 4) +
-         align256(B * Vo * 12) + align256(B * 32);
+static VertexSdf vertex_sdf(Bump& w, long B, long V) {
+  VertexSdf v;
+  v.sdf = w.floats(B * V);
+  v.face = w.ints(B * V);
+  v.bary = w.floats(B * V * 3);
+  return v;
 }
-
-static LossWorkspace carve_loss(char* w, long B, long Vh, long Fh, long Vo, long Fo) {
+static LossWorkspace loss_workspace(Bump& w, long B, long Vh, long Fh, long Vo, long Fo) {
   LossWorkspace s;
-  s.mh = carve(w, B, Fh); w += mesh_buffers_bytes(B, Fh);
-  s.mo = carve(w, B, Fo); w += mesh_buffers_bytes(B, Fo);
-  s.sdf_ho = (float*)w; w += align256(B * Vh * 4);
-  s.face_ho = (int32_t*)w; w += align256(B * Vh * 4);
-  s.bary_ho = (float*)w; w += align256(B * Vh * 12);
-  s.sdf_oh = (float*)w; w += align256(B * Vo * 4);
-  s.face_oh = (int32_t*)w; w += align256(B * Vo * 4);
-  s.bary_oh = (float*)w; w += align256(B * Vo * 12);
-  s.den = (double*)w;
+  s.m = mesh_pair(w, B, Fh, Fo);
+  s.ho = vertex_sdf(w, B, Vh);
+  s.oh = vertex_sdf(w, B, Vo);
+  s.den = (double*)w.take(B * 32);
   return s;
 }
 
 struct LossWeights { const float *rep_w_hand, *att_w_hand, *rep_w_obj; long s_rep_hand, s_att_hand, s_rep_obj; };
 
-// every check the two entries share, before any launch; > 0: B = 0, nothing to do
+// every check the two entries share, before any launch, and the workspace laid out into *s; > 0: B = 0, nothing to do
 static int loss_check(const char* what, const hoisdf_mesh* hand, const hoisdf_mesh* obj, int B, const LossWeights& w, float alpha,
-                      const void* workspace, long workspace_bytes) {
-  HOISDF_REQUIRE(hand && obj, HOISDF_ERR_INVALID, "%s: null pointer (hand, obj)", what);
-  if (!mesh_shape_ok(what, B, hand->V, hand->max_faces) || !mesh_shape_ok(what, B, obj->V, obj->max_faces)) return HOISDF_ERR_INVALID;
+                      const void* workspace, long workspace_bytes, LossWorkspace* s) {
+  if (!mesh_desc_ok(what, "hand", hand, B) || !mesh_desc_ok(what, "obj", obj, B)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(alpha > 0.f && alpha <= 3.0e38f, HOISDF_ERR_INVALID, "%s: alpha=%g (> 0, finite)", what, (double)alpha);
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->face_batch_stride == 0 || m->face_batch_stride >= 3L * m->max_faces, HOISDF_ERR_INVALID,
-                   "%s: face_batch_stride=%ld (0 or >= 3 max_faces)", what, m->face_batch_stride);
   HOISDF_REQUIRE(w.s_rep_hand == 0 || w.s_rep_hand == hand->V, HOISDF_ERR_INVALID, "%s: rep_w_hand_stride=%ld (0 or hand V)", what, w.s_rep_hand);
   HOISDF_REQUIRE(w.s_att_hand == 0 || w.s_att_hand == hand->V, HOISDF_ERR_INVALID, "%s: att_w_hand_stride=%ld (0 or hand V)", what, w.s_att_hand);
   HOISDF_REQUIRE(w.s_rep_obj == 0 || w.s_rep_obj == obj->V, HOISDF_ERR_INVALID, "%s: rep_w_obj_stride=%ld (0 or obj V)", what, w.s_rep_obj);
   if (B == 0) return 1;
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->V > 0 && m->verts && (m->max_faces == 0 || m->faces), HOISDF_ERR_INVALID,
-                   "%s: null pointer (verts, faces) or a mesh without vertices", what);
+  if (!mesh_data_ok(what, "hand", hand) || !mesh_data_ok(what, "obj", obj)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(workspace, HOISDF_ERR_INVALID, "%s: null pointer (workspace)", what);
-  const long need = loss_workspace_bytes(B, hand->V, hand->max_faces, obj->V, obj->max_faces);
-  HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "%s: workspace of %ld bytes, %ld needed", what, workspace_bytes, need);
+  Bump bump(const_cast<void*>(workspace), workspace_bytes);
+  *s = loss_workspace(bump, B, hand->V, hand->max_faces, obj->V, obj->max_faces);
+  HOISDF_REQUIRE(workspace_bytes >= bump.bytes(), HOISDF_ERR_INVALID, "%s: workspace of %ld bytes, %ld needed", what, workspace_bytes,
+                 bump.bytes());
   return 0;
 }
 
 static void loss_queries(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, const LossWeights& w,
                          const LossWorkspace& s, const float* g_rep_hand, const float* g_att, const float* g_rep_obj, LossQueries* ho,
                          LossQueries* oh) {
-  *ho = {hand->verts, hand->V, nullptr, hand->n_faces, hand->max_faces, s.mo.tris, s.mo.box, obj->max_faces, s.sdf_ho, s.face_ho, s.bary_ho, w.rep_w_hand, w.s_rep_hand,
+  *ho = {hand->verts, hand->V, nullptr, hand->n_faces, hand->max_faces, s.m.obj.tris, s.m.obj.box, obj->max_faces, s.ho.sdf, s.ho.face, s.ho.bary, w.rep_w_hand, w.s_rep_hand,
          w.att_w_hand, w.s_att_hand, 1, g_rep_hand, g_att, 0, 1};
-  *oh = {obj->verts, obj->V, obj_n_verts, obj->n_faces, obj->max_faces, s.mh.tris, s.mh.box, hand->max_faces, s.sdf_oh, s.face_oh, s.bary_oh, w.rep_w_obj, w.s_rep_obj,
+  *oh = {obj->verts, obj->V, obj_n_verts, obj->n_faces, obj->max_faces, s.m.hand.tris, s.m.hand.box, hand->max_faces, s.oh.sdf, s.oh.face, s.oh.bary, w.rep_w_obj, w.s_rep_obj,
          nullptr, 0, 0, g_rep_obj, nullptr, 2, 2};
 }
 
@@ -249,11 +243,14 @@ static void loss_queries(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const 
 
 using namespace hoisdf;
 
+
 extern "C" long hoisdf_interaction_loss_workspace_bytes(int B, int hand_V, int hand_max_faces, int obj_V, int obj_max_faces) {
   if (!mesh_shape_ok("interaction_loss_workspace_bytes (hand)", B, hand_V, hand_max_faces) ||
       !mesh_shape_ok("interaction_loss_workspace_bytes (obj)", B, obj_V, obj_max_faces))
     return -1;
-  return loss_workspace_bytes(B, hand_V, hand_max_faces, obj_V, obj_max_faces);
+  Bump w(nullptr, 0);
+  loss_workspace(w, B, hand_V, hand_max_faces, obj_V, obj_max_faces);
+  return w.bytes();
 }
 
 extern "C" int hoisdf_interaction_loss_fwd(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* obj_n_verts, int B,
@@ -262,20 +259,12 @@ extern "C" int hoisdf_interaction_loss_fwd(const hoisdf_mesh* hand, const hoisdf
                                            float* rep_hand, float* att, float* rep_obj, void* workspace, long workspace_bytes,
                                            void* stream) {
   const LossWeights w = {rep_w_hand, att_w_hand, rep_w_obj, rep_w_hand_stride, att_w_hand_stride, rep_w_obj_stride};
-  const int rc = loss_check("interaction_loss_fwd", hand, obj, B, w, alpha, workspace, workspace_bytes);
+  LossWorkspace s;
+  const int rc = loss_check("interaction_loss_fwd", hand, obj, B, w, alpha, workspace, workspace_bytes, &s);
   if (rc != 0) return rc > 0 ? HOISDF_OK : rc;
   HOISDF_REQUIRE(rep_hand && att && rep_obj, HOISDF_ERR_INVALID, "interaction_loss_fwd: null pointer (rep_hand, att, rep_obj)");
   hipStream_t st = as_stream(stream);
-  const LossWorkspace s = carve_loss((char*)workspace, B, hand->V, hand->max_faces, obj->V, obj->max_faces);
-  launch_prepare(hand->verts, B, hand->V, hand->faces, hand->face_batch_stride, hand->n_faces, hand->max_faces, s.mh, st);
-  launch_prepare(obj->verts, B, obj->V, obj->faces, obj->face_batch_stride, obj->n_faces, obj->max_faces, s.mo, st);
-  // every hand vertex against the object, every object vertex (padding rows too: the reduction leaves them out) against the hand
-  MeshSdfArgs ho = {hand->verts, 3, s.mo.tris, s.mo.box, obj->n_faces, obj->max_faces, hand->V, s.sdf_ho, 1, s.face_ho, s.bary_ho, nullptr,
-                    nullptr, 0, nullptr, nullptr, 0.f, 0};
-  launch_sdf(ho, B, st);
-  MeshSdfArgs oh = {obj->verts, 3, s.mh.tris, s.mh.box, hand->n_faces, hand->max_faces, obj->V, s.sdf_oh, 1, s.face_oh, s.bary_oh, nullptr,
-                    nullptr, 0, nullptr, nullptr, 0.f, 0};
-  launch_sdf(oh, B, st);
+  launch_both_ways(*hand, *obj, B, s.m, s.ho, s.oh, st);
   LossReduceArgs ra;
   loss_queries(hand, obj, obj_n_verts, w, s, nullptr, nullptr, nullptr, &ra.ho, &ra.oh);
   ra.alpha = alpha;
@@ -291,11 +280,11 @@ extern "C" int hoisdf_interaction_loss_bwd(const hoisdf_mesh* hand, const hoisdf
                                            const float* g_rep_hand, const float* g_att, const float* g_rep_obj, float* d_hand_verts,
                                            float* d_obj_verts, const void* workspace, long workspace_bytes, void* stream) {
   const LossWeights w = {rep_w_hand, att_w_hand, rep_w_obj, rep_w_hand_stride, att_w_hand_stride, rep_w_obj_stride};
-  const int rc = loss_check("interaction_loss_bwd", hand, obj, B, w, alpha, workspace, workspace_bytes);
+  LossWorkspace s;
+  const int rc = loss_check("interaction_loss_bwd", hand, obj, B, w, alpha, workspace, workspace_bytes, &s);
   if (rc != 0) return rc > 0 ? HOISDF_OK : rc;
   HOISDF_REQUIRE(d_hand_verts && d_obj_verts, HOISDF_ERR_INVALID, "interaction_loss_bwd: null pointer (d_hand_verts, d_obj_verts)");
   hipStream_t st = as_stream(stream);
-  const LossWorkspace s = carve_loss((char*)workspace, B, hand->V, hand->max_faces, obj->V, obj->max_faces);
   LossQueries ho, oh;
   loss_queries(hand, obj, obj_n_verts, w, s, g_rep_hand, g_att, g_rep_obj, &ho, &oh);
   const LossBwdArgs to_hand = {ho, oh, s.den, alpha, d_hand_verts}, to_obj = {oh, ho, s.den, alpha, d_obj_verts};

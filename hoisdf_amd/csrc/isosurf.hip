@@ -303,9 +303,15 @@ static bool iso_shape_ok(const char* what, int B, int n) {
   return true;
 }
 static long iso_nodes(int n) { return (long)n * n * n; }
-static long iso_workspace_bytes(long B, int n) {
+// workspace of hoisdf_iso_extract: the per-block vertex and face counts, then one word per node
+struct IsoWorkspace { int32_t *blk_v, *blk_f; uint32_t* word; };
+static IsoWorkspace iso_workspace(Bump& w, long B, int n) {
   const long nblk = cdiv(iso_nodes(n), ISO_T);
-  return 2 * align256(B * nblk * 4) + align256(B * iso_nodes(n) * 4);
+  IsoWorkspace s;
+  s.blk_v = w.ints(B * nblk);
+  s.blk_f = w.ints(B * nblk);
+  s.word = (uint32_t*)w.take(B * iso_nodes(n) * 4);
+  return s;
 }
 
 // ---- d. Chamfer distance of predicted vertices to a ground-truth mesh -------------------------------------------------------------------
@@ -382,8 +388,15 @@ __global__ __launch_bounds__(ISO_T) void surf_reduce_kernel(const float* __restr
   n_used[b] = usable ? nv : 0;
 }
 
-static long surf_workspace_bytes(long B, long max_verts, long max_faces, long n_samples) {
-  return mesh_buffers_bytes(B, max_faces) + align256(B * max_verts * 4) + align256(B * n_samples * 12) + align256(B * n_samples * 4);
+// workspace of hoisdf_eval_surface: the prepared mesh, a distance per predicted vertex, the surface samples, their squared distances
+struct SurfWorkspace { MeshBuffers m; float *sdf, *samples, *d2; };
+static SurfWorkspace surf_workspace(Bump& w, long B, long max_verts, long max_faces, long n_samples) {
+  SurfWorkspace s;
+  s.m = mesh_buffers(w, B, max_faces);
+  s.sdf = w.floats(B * max_verts);
+  s.samples = w.floats(B * n_samples * 3);
+  s.d2 = w.floats(B * n_samples);
+  return s;
 }
 static bool surf_shape_ok(const char* what, int B, int max_verts, int max_faces, int n_samples) {
   if (!mesh_shape_ok(what, B, 0, max_faces)) return false;
@@ -423,7 +436,9 @@ extern "C" int hoisdf_iso_refine_grid(const float* values, int ld, const float* 
 
 extern "C" long hoisdf_iso_extract_workspace_bytes(int B, int n) {
   if (!iso_shape_ok("iso_extract_workspace_bytes", B, n)) return -1;
-  return iso_workspace_bytes(B, n);
+  Bump w(nullptr, 0);
+  iso_workspace(w, B, n);
+  return w.bytes();
 }
 
 extern "C" int hoisdf_iso_extract(const float* values, int ld, const float* grid, int n, int B, float iso, float out_scale,
@@ -436,17 +451,15 @@ extern "C" int hoisdf_iso_extract(const float* values, int ld, const float* grid
   if (B == 0) return HOISDF_OK;
   HOISDF_REQUIRE(values && grid && n_verts && n_faces, HOISDF_ERR_INVALID, "iso_extract: null pointer (values, grid, n_verts, n_faces)");
   HOISDF_REQUIRE(workspace, HOISDF_ERR_INVALID, "iso_extract: null pointer (workspace)");
-  const long need = iso_workspace_bytes(B, n);
-  HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "iso_extract: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  Bump w(workspace, workspace_bytes);
+  const IsoWorkspace s = iso_workspace(w, B, n);
+  HOISDF_REQUIRE(workspace_bytes >= w.bytes(), HOISDF_ERR_INVALID, "iso_extract: workspace of %ld bytes, %ld needed", workspace_bytes, w.bytes());
   hipStream_t st = as_stream(stream);
   const int nblk = cdiv(iso_nodes(n), ISO_T);
-  char* w = (char*)workspace;
   IsoArgs a;
   a.values = values; a.ld = ld; a.grid = grid; a.n = n; a.iso = iso;
-  a.blk_v = (int32_t*)w; w += align256((long)B * nblk * 4);
-  a.blk_f = (int32_t*)w; w += align256((long)B * nblk * 4);
-  a.nblk = nblk;
-  a.word = (uint32_t*)w;
+  a.blk_v = s.blk_v; a.blk_f = s.blk_f; a.nblk = nblk;
+  a.word = s.word;
   a.out_scale = out_scale; a.out_shift = out_shift;
   a.verts = verts; a.max_verts = verts ? max_verts : 0;
   a.faces = faces; a.max_faces = faces ? max_faces : 0;
@@ -460,47 +473,35 @@ extern "C" int hoisdf_iso_extract(const float* values, int ld, const float* grid
 
 extern "C" long hoisdf_eval_surface_workspace_bytes(int B, int max_verts, int gt_max_faces, int n_samples) {
   if (!surf_shape_ok("eval_surface_workspace_bytes", B, max_verts, gt_max_faces, n_samples)) return -1;
-  return surf_workspace_bytes(B, max_verts, gt_max_faces, n_samples);
+  Bump w(nullptr, 0);
+  surf_workspace(w, B, max_verts, gt_max_faces, n_samples);
+  return w.bytes();
 }
 
 extern "C" int hoisdf_eval_surface(const float* pred_verts, const int32_t* pred_n_verts, int max_verts, const hoisdf_mesh* gt, int B,
                                    int n_samples, uint64_t seed, float* pred_to_gt, float* gt_to_pred, float* chamfer, int32_t* n_used,
                                    float* samples_out, int32_t* nearest_out, void* workspace, long workspace_bytes, void* stream) {
-  HOISDF_REQUIRE(gt, HOISDF_ERR_INVALID, "eval_surface: null pointer (gt)");
-  if (!mesh_shape_ok("eval_surface (gt)", B, gt->V, gt->max_faces) || !surf_shape_ok("eval_surface", B, max_verts, gt->max_faces, n_samples))
+  if (!mesh_desc_ok("eval_surface", "gt", gt, B) || !surf_shape_ok("eval_surface", B, max_verts, gt->max_faces, n_samples))
     return HOISDF_ERR_INVALID;
-  HOISDF_REQUIRE(gt->face_batch_stride == 0 || gt->face_batch_stride >= 3L * gt->max_faces, HOISDF_ERR_INVALID,
-                 "eval_surface: face_batch_stride=%ld (0 or >= 3 max_faces)", gt->face_batch_stride);
   if (B == 0) return HOISDF_OK;
-  HOISDF_REQUIRE(gt->V > 0 && gt->verts && (gt->max_faces == 0 || gt->faces), HOISDF_ERR_INVALID,
-                 "eval_surface: null pointer (gt verts, faces) or a mesh without vertices");
+  if (!mesh_data_ok("eval_surface", "gt", gt)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(pred_n_verts && (max_verts == 0 || pred_verts), HOISDF_ERR_INVALID, "eval_surface: null pointer (pred_verts, pred_n_verts)");
   HOISDF_REQUIRE(pred_to_gt && gt_to_pred && chamfer && n_used, HOISDF_ERR_INVALID,
                  "eval_surface: null pointer (pred_to_gt, gt_to_pred, chamfer, n_used)");
   HOISDF_REQUIRE(workspace, HOISDF_ERR_INVALID, "eval_surface: null pointer (workspace)");
-  const long need = surf_workspace_bytes(B, max_verts, gt->max_faces, n_samples);
-  HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "eval_surface: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  Bump w(workspace, workspace_bytes);
+  const SurfWorkspace s = surf_workspace(w, B, max_verts, gt->max_faces, n_samples);
+  HOISDF_REQUIRE(workspace_bytes >= w.bytes(), HOISDF_ERR_INVALID, "eval_surface: workspace of %ld bytes, %ld needed", workspace_bytes, w.bytes());
   hipStream_t st = as_stream(stream);
-  char* w = (char*)workspace;
-  const MeshBuffers m = carve(w, B, gt->max_faces);
-  w += mesh_buffers_bytes(B, gt->max_faces);
-  float* sdf = (float*)w;
-  w += align256((long)B * max_verts * 4);
-  float* samples = samples_out ? samples_out : (float*)w;
-  w += align256((long)B * n_samples * 12);
-  float* d2 = (float*)w;
-  launch_prepare(gt->verts, B, gt->V, gt->faces, gt->face_batch_stride, gt->n_faces, gt->max_faces, m, st);
+  float* samples = samples_out ? samples_out : s.samples;
+  launch_prepare(*gt, B, s.m, st);
   // every row of pred_verts against the mesh (rows from pred_n_verts[b] on are left out in the reduction)
-  if (max_verts) {
-    MeshSdfArgs pa = {pred_verts, 3, m.tris, m.box, gt->n_faces, gt->max_faces, max_verts, sdf, 1, nullptr, nullptr, nullptr,
-                      nullptr, 0, nullptr, nullptr, 0.f, 0};
-    launch_sdf(pa, B, st);
-  }
+  if (max_verts) launch_sdf(sdf_args(pred_verts, 3, max_verts, s.m, gt->n_faces, gt->max_faces, s.sdf, 1), B, st);
   // sigma 0 and no box points: a + s (b - a) ... in barycentric form + 0 x noise, exactly a point of the face drawn by area
-  launch_sample(m, gt->n_faces, gt->max_faces, B, n_samples, 0.f, 0.f, 0, 0.f, seed, samples, (long)n_samples * 3, 3, nullptr, st);
+  launch_sample(s.m, gt->n_faces, gt->max_faces, B, n_samples, 0.f, 0.f, 0, 0.f, seed, samples, (long)n_samples * 3, 3, nullptr, st);
   hipLaunchKernelGGL(surf_nn_kernel, dim3(cdiv(n_samples, ISO_T), B), dim3(ISO_T), 0, st, samples, n_samples, pred_verts, pred_n_verts,
-                     max_verts, d2, nearest_out);
-  hipLaunchKernelGGL(surf_reduce_kernel, dim3(B), dim3(ISO_T), 0, st, sdf, pred_n_verts, max_verts, d2, n_samples, m.box, pred_to_gt,
+                     max_verts, s.d2, nearest_out);
+  hipLaunchKernelGGL(surf_reduce_kernel, dim3(B), dim3(ISO_T), 0, st, s.sdf, pred_n_verts, max_verts, s.d2, n_samples, s.m.box, pred_to_gt,
                      gt_to_pred, chamfer, n_used);
   return check_launch("eval_surface");
 }

@@ -1,7 +1,7 @@
-// What mesh_sdf.hip (point-to-mesh signed distance) and interact.hip (hand-object interaction metrics) share: the small vector
-// helpers, the skipped-face rule's unfused cross product, the polynomial atan2 of the solid angle, the argument block of
-// mesh_sdf_kernel, the carving of the prepared-mesh buffers out of a workspace and the launches of the two kernels both files run
-// (defined in mesh_sdf.hip, where the kernels are).
+// What the mesh entries (mesh_sdf.hip, interact.hip, interact_loss.hip, isosurf.hip, raster.hip) share: the small vector helpers,
+// the skipped-face rule's unfused cross product, the polynomial atan2 of the solid angle, the argument block of mesh_sdf_kernel,
+// the layout of the prepared-mesh buffers inside a workspace, the check of a hoisdf_mesh descriptor and the launches of the kernels
+// several files run (defined in mesh_sdf.hip, where the kernels are).
 #pragma once
 #include "common.h"
 
@@ -66,24 +66,51 @@ __device__ __forceinline__ float atan2_poly(float y, float x) {
 }
 
 // ---- the prepared mesh of a batch inside a workspace, and the launches (mesh_sdf.hip) --------------------------------------------
+// Every workspace of the family has ONE layout function over a Bump (common.h): measuring (null base) it is the size query, over
+// the caller's buffer it makes the pointers of the call.
 struct MeshBuffers { float4* tris; float* area; float* cdf; float* box; };
-static inline long align256(long n) { return (n + 255) / 256 * 256; }
-static inline long mesh_buffers_bytes(long B, long max_faces) {
-  return align256(B * max_faces * 48) + 2 * align256(B * max_faces * 4) + align256(B * 32);
-}
-static inline MeshBuffers carve(char* base, long B, long max_faces) {
+static inline MeshBuffers mesh_buffers(Bump& w, long B, long max_faces) {
   MeshBuffers m;
-  m.tris = (float4*)base; base += align256(B * max_faces * 48);
-  m.area = (float*)base; base += align256(B * max_faces * 4);
-  m.cdf = (float*)base; base += align256(B * max_faces * 4);
-  m.box = (float*)base;
+  m.tris = (float4*)w.take(B * max_faces * 48);
+  m.area = w.floats(B * max_faces);
+  m.cdf = w.floats(B * max_faces);
+  m.box = w.floats(B * 8);
   return m;
+}
+// the hand's, then the object's: all of hoisdf_mesh_sdf_rows' workspace and the head of the two interaction workspaces
+struct MeshPair { MeshBuffers hand, obj; };
+static inline MeshPair mesh_pair(Bump& w, long B, long hand_max_faces, long obj_max_faces) {
+  MeshPair p;
+  p.hand = mesh_buffers(w, B, hand_max_faces);
+  p.obj = mesh_buffers(w, B, obj_max_faces);
+  return p;
 }
 
 bool mesh_shape_ok(const char* what, int B, int V, int max_faces);
-void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long face_stride, const int32_t* n_faces, int max_faces,
-                    const MeshBuffers& m, hipStream_t st);
+// The rules of a hoisdf_mesh descriptor, in two steps because B == 0 returns HOISDF_OK between them.  `what` names the entry,
+// `name` the mesh (hand, obj, gt); a null descriptor passes both only where the entry allows an absent mesh.
+//   mesh_desc_ok  before B == 0: the descriptor is there, the shape limits (mesh_shape_ok), face_batch_stride 0 or >= 3 max_faces
+//   mesh_data_ok  after it: V > 0, verts, and faces where max_faces > 0
+bool mesh_desc_ok(const char* what, const char* name, const hoisdf_mesh* m, int B, bool may_be_absent = false);
+bool mesh_data_ok(const char* what, const char* name, const hoisdf_mesh* m);
+
+void launch_prepare(const hoisdf_mesh& mesh, int B, const MeshBuffers& m, hipStream_t st);
+// the plain case: N points per sample against a prepared mesh, the distance alone; whoever wants the winning face, the weights or
+// the labels sets those fields afterwards
+static inline MeshSdfArgs sdf_args(const float* points, int ldp, int N, const MeshBuffers& m, const int32_t* n_faces, int max_faces,
+                                   float* sdf, int ld) {
+  MeshSdfArgs a = {};
+  a.points = points; a.ldp = ldp; a.N = N;
+  a.tris = m.tris; a.box = m.box; a.n_faces = n_faces; a.max_faces = max_faces;
+  a.sdf = sdf; a.ld = ld;
+  return a;
+}
 void launch_sdf(const MeshSdfArgs& a, int B, hipStream_t st);
+// Both meshes prepared, then every hand vertex against the object and every object vertex (padding rows too) against the hand:
+// 4 launches, in this order.  Where a direction leaves its [B][V] distances and, if wanted, winning faces and [B][V][3] weights.
+struct VertexSdf { float* sdf; int32_t* face; float* bary; };
+void launch_both_ways(const hoisdf_mesh& hand, const hoisdf_mesh& obj, int B, const MeshPair& m, const VertexSdf& hand_to_obj,
+                      const VertexSdf& obj_to_hand, hipStream_t st);
 // N points per sample into points[b pstride + i ldp + 0..2] (hoisdf_mesh_sample_points; isosurf.hip draws its surface points with it)
 void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, int B, int N, float s1, float s2, int every, float pad,
                    uint64_t seed, float* points, long pstride, int ldp, int32_t* face_out, hipStream_t st);

@@ -19,8 +19,8 @@
 // The four partial answers of a point meet in LDS and wave 0 combines them in wave order: strictly nearer wins, the LOWER face
 // index on an exact tie - so the nearest face is the lowest index among equals whatever the tile and wave order - and the angle
 // sums are added in one fixed order.
-// The vector helpers, atan2_poly, MeshSdfArgs, the workspace carving and the declarations of the two launches that interact.hip
-// runs as well are in mesh.h.
+// The vector helpers, atan2_poly, MeshSdfArgs, the workspace layout and the declarations of the descriptor check and the launches
+// that the other mesh files run as well are in mesh.h.
 #include "mesh.h"
 
 namespace hoisdf {
@@ -268,10 +268,31 @@ bool mesh_shape_ok(const char* what, int B, int V, int max_faces) {
   return true;
 }
 
-void launch_prepare(const float* verts, int B, int V, const int32_t* faces, long face_stride, const int32_t* n_faces, int max_faces,
-                    const MeshBuffers& m, hipStream_t st) {
-  hipLaunchKernelGGL(mesh_prepare_kernel, dim3(B), dim3(256), 0, st, verts, V, faces, face_stride, n_faces, max_faces, m.tris, m.area,
-                     m.cdf, m.box);
+bool mesh_desc_ok(const char* what, const char* name, const hoisdf_mesh* m, int B, bool may_be_absent) {
+  if (!m) {
+    if (!may_be_absent) set_error("%s: null pointer (%s)", what, name);
+    return may_be_absent;
+  }
+  char label[96];
+  snprintf(label, sizeof label, "%s (%s)", what, name);
+  if (!mesh_shape_ok(label, B, m->V, m->max_faces)) return false;
+  if (m->face_batch_stride != 0 && m->face_batch_stride < 3L * m->max_faces) {
+    set_error("%s: %s face_batch_stride=%ld (0 or >= 3 max_faces)", what, name, m->face_batch_stride);
+    return false;
+  }
+  return true;
+}
+bool mesh_data_ok(const char* what, const char* name, const hoisdf_mesh* m) {
+  if (m && !(m->V > 0 && m->verts && (m->max_faces == 0 || m->faces))) {
+    set_error("%s: null pointer (%s verts, faces) or a mesh without vertices", what, name);
+    return false;
+  }
+  return true;
+}
+
+void launch_prepare(const hoisdf_mesh& mesh, int B, const MeshBuffers& m, hipStream_t st) {
+  hipLaunchKernelGGL(mesh_prepare_kernel, dim3(B), dim3(256), 0, st, mesh.verts, mesh.V, mesh.faces, mesh.face_batch_stride, mesh.n_faces,
+                     mesh.max_faces, m.tris, m.area, m.cdf, m.box);
 }
 void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, int B, int N, float s1, float s2, int every,
                           float pad, uint64_t seed, float* points, long pstride, int ldp, int32_t* face_out, hipStream_t st) {
@@ -280,6 +301,17 @@ void launch_sample(const MeshBuffers& m, const int32_t* n_faces, int max_faces, 
 }
 void launch_sdf(const MeshSdfArgs& a, int B, hipStream_t st) {
   hipLaunchKernelGGL(mesh_sdf_kernel, dim3(cdiv(a.N, MESH_PTS), B), dim3(256), 0, st, a);
+}
+void launch_both_ways(const hoisdf_mesh& hand, const hoisdf_mesh& obj, int B, const MeshPair& m, const VertexSdf& hand_to_obj,
+                      const VertexSdf& obj_to_hand, hipStream_t st) {
+  launch_prepare(hand, B, m.hand, st);
+  launch_prepare(obj, B, m.obj, st);
+  MeshSdfArgs ho = sdf_args(hand.verts, 3, hand.V, m.obj, obj.n_faces, obj.max_faces, hand_to_obj.sdf, 1);
+  ho.face_out = hand_to_obj.face; ho.bary_out = hand_to_obj.bary;
+  launch_sdf(ho, B, st);
+  MeshSdfArgs oh = sdf_args(obj.verts, 3, obj.V, m.hand, hand.n_faces, hand.max_faces, obj_to_hand.sdf, 1);
+  oh.face_out = obj_to_hand.face; oh.bary_out = obj_to_hand.bary;
+  launch_sdf(oh, B, st);
 }
 
 }  // namespace hoisdf
@@ -296,7 +328,7 @@ extern "C" int hoisdf_mesh_prepare(const float* verts, int B, int V, const int32
   HOISDF_REQUIRE(box && (V == 0 || verts), HOISDF_ERR_INVALID, "mesh_prepare: null pointer (verts, box)");
   HOISDF_REQUIRE(max_faces == 0 || (V > 0 && faces && tris && area && cdf), HOISDF_ERR_INVALID,
                  "mesh_prepare: null pointer (faces, tris, area, cdf) or faces without vertices");
-  launch_prepare(verts, B, V, faces, face_batch_stride, n_faces, max_faces, {(float4*)tris, area, cdf, box}, as_stream(stream));
+  launch_prepare({verts, faces, n_faces, face_batch_stride, V, max_faces}, B, {(float4*)tris, area, cdf, box}, as_stream(stream));
   return check_launch("mesh_prepare");
 }
 
@@ -323,8 +355,9 @@ extern "C" int hoisdf_mesh_sdf(const float* points, int ldp, int B, int N, const
   if (B == 0 || N == 0) return HOISDF_OK;
   HOISDF_REQUIRE(points && box && sdf && (max_faces == 0 || tris), HOISDF_ERR_INVALID, "mesh_sdf: null pointer");
   HOISDF_REQUIRE(!label_out || vert_label, HOISDF_ERR_INVALID, "mesh_sdf: null pointer (label_out without vert_label)");
-  MeshSdfArgs a = {points, ldp, (const float4*)tris, box, n_faces, max_faces, N, sdf, ld, face_out, bary_out, winding_out,
-                   vert_label, label_batch_stride, label_out, nullptr, 0.f, 0};
+  MeshSdfArgs a = sdf_args(points, ldp, N, {(float4*)tris, nullptr, nullptr, (float*)box}, n_faces, max_faces, sdf, ld);
+  a.face_out = face_out; a.bary_out = bary_out; a.winding_out = winding_out;
+  a.vert_label = vert_label; a.label_stride = label_batch_stride; a.label_out = label_out;
   launch_sdf(a, B, as_stream(stream));
   return check_launch("mesh_sdf");
 }
@@ -333,47 +366,39 @@ extern "C" long hoisdf_mesh_sdf_rows_workspace_bytes(int B, int hand_max_faces, 
   if (!mesh_shape_ok("mesh_sdf_rows_workspace_bytes", B, 0, hand_max_faces) ||
       !mesh_shape_ok("mesh_sdf_rows_workspace_bytes", B, 0, obj_max_faces))
     return -1;
-  return mesh_buffers_bytes(B, hand_max_faces) + mesh_buffers_bytes(B, obj_max_faces);
+  Bump w(nullptr, 0);
+  mesh_pair(w, B, hand_max_faces, obj_max_faces);
+  return w.bytes();
 }
 
 extern "C" int hoisdf_mesh_sdf_rows(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const int32_t* hand_vert_label, int B, int n_hand,
                                     int n_obj, float sigma1, float sigma2, int uniform_every, float pad, float clamp, uint64_t seed,
                                     float* rows, int ld, void* workspace, long workspace_bytes, void* stream) {
-  HOISDF_REQUIRE(hand && obj, HOISDF_ERR_INVALID, "mesh_sdf_rows: null pointer (hand, obj)");
-  if (!mesh_shape_ok("mesh_sdf_rows (hand)", B, hand->V, hand->max_faces) || !mesh_shape_ok("mesh_sdf_rows (obj)", B, obj->V, obj->max_faces))
-    return HOISDF_ERR_INVALID;
+  if (!mesh_desc_ok("mesh_sdf_rows", "hand", hand, B) || !mesh_desc_ok("mesh_sdf_rows", "obj", obj, B)) return HOISDF_ERR_INVALID;
   const long n = (long)n_hand + n_obj;
   HOISDF_REQUIRE(n_hand >= 0 && n_obj >= 0 && n <= (1 << 28) && ld >= 6, HOISDF_ERR_INVALID,
                  "mesh_sdf_rows: n_hand=%d n_obj=%d (>= 0, sum <= 2^28) ld=%d (>= 6)", n_hand, n_obj, ld);
   HOISDF_REQUIRE(sigma1 >= 0.f && sigma2 >= 0.f && pad >= 0.f && clamp >= 0.f, HOISDF_ERR_INVALID,
                  "mesh_sdf_rows: sigma1=%g sigma2=%g pad=%g clamp=%g (>= 0)", (double)sigma1, (double)sigma2, (double)pad, (double)clamp);
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->face_batch_stride == 0 || m->face_batch_stride >= 3L * m->max_faces, HOISDF_ERR_INVALID,
-                   "mesh_sdf_rows: face_batch_stride=%ld (0 or >= 3 max_faces)", m->face_batch_stride);
   if (B == 0 || n == 0) return HOISDF_OK;
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(m->V > 0 && m->verts && (m->max_faces == 0 || m->faces), HOISDF_ERR_INVALID,
-                   "mesh_sdf_rows: null pointer (verts, faces) or a mesh without vertices");
+  if (!mesh_data_ok("mesh_sdf_rows", "hand", hand) || !mesh_data_ok("mesh_sdf_rows", "obj", obj)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(rows && workspace && hand_vert_label, HOISDF_ERR_INVALID, "mesh_sdf_rows: null pointer (rows, workspace, hand_vert_label)");
-  const long need = mesh_buffers_bytes(B, hand->max_faces) + mesh_buffers_bytes(B, obj->max_faces);
-  HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "mesh_sdf_rows: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  Bump w(workspace, workspace_bytes);
+  const MeshPair m = mesh_pair(w, B, hand->max_faces, obj->max_faces);
+  HOISDF_REQUIRE(workspace_bytes >= w.bytes(), HOISDF_ERR_INVALID, "mesh_sdf_rows: workspace of %ld bytes, %ld needed", workspace_bytes, w.bytes());
   hipStream_t st = as_stream(stream);
-  const MeshBuffers mh = carve((char*)workspace, B, hand->max_faces);
-  const MeshBuffers mo = carve((char*)workspace + mesh_buffers_bytes(B, hand->max_faces), B, obj->max_faces);
-  launch_prepare(hand->verts, B, hand->V, hand->faces, hand->face_batch_stride, hand->n_faces, hand->max_faces, mh, st);
-  launch_prepare(obj->verts, B, obj->V, obj->faces, obj->face_batch_stride, obj->n_faces, obj->max_faces, mo, st);
+  launch_prepare(*hand, B, m.hand, st);
+  launch_prepare(*obj, B, m.obj, st);
   // the row block of sample b: n_hand points drawn at the hand, then n_obj drawn at the object, the points written straight into
   // columns 0-2; two seeds, so that the two sets do not share their draws
   const long rs = n * ld;
-  if (n_hand) launch_sample(mh, hand->n_faces, hand->max_faces, B, n_hand, sigma1, sigma2, uniform_every, pad, seed * 2, rows, rs, ld, nullptr, st);
-  if (n_obj) launch_sample(mo, obj->n_faces, obj->max_faces, B, n_obj, sigma1, sigma2, uniform_every, pad, seed * 2 + 1,
+  if (n_hand) launch_sample(m.hand, hand->n_faces, hand->max_faces, B, n_hand, sigma1, sigma2, uniform_every, pad, seed * 2, rows, rs, ld, nullptr, st);
+  if (n_obj) launch_sample(m.obj, obj->n_faces, obj->max_faces, B, n_obj, sigma1, sigma2, uniform_every, pad, seed * 2 + 1,
                            rows + (size_t)n_hand * ld, rs, ld, nullptr, st);
   // every row against both meshes: sdf_hand -> column 3 with the label -> column 5, sdf_obj -> column 4
-  MeshSdfArgs a = {rows, ld, mh.tris, mh.box, hand->n_faces, hand->max_faces, (int)n, rows + 3, ld, nullptr, nullptr, nullptr,
-                   hand_vert_label, 0, nullptr, rows + 5, clamp, n_hand};
+  MeshSdfArgs a = sdf_args(rows, ld, (int)n, m.hand, hand->n_faces, hand->max_faces, rows + 3, ld);
+  a.vert_label = hand_vert_label; a.label_f = rows + 5; a.clamp = clamp; a.n_label = n_hand;
   launch_sdf(a, B, st);
-  MeshSdfArgs o = {rows, ld, mo.tris, mo.box, obj->n_faces, obj->max_faces, (int)n, rows + 4, ld, nullptr, nullptr, nullptr,
-                   nullptr, 0, nullptr, nullptr, 0.f, 0};
-  launch_sdf(o, B, st);
+  launch_sdf(sdf_args(rows, ld, (int)n, m.obj, obj->n_faces, obj->max_faces, rows + 4, ld), B, st);
   return check_launch("mesh_sdf_rows");
 }

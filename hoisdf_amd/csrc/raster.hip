@@ -255,16 +255,11 @@ __global__ __launch_bounds__(RASTER_T) void silhouette_kernel(const float* __res
   if (tid < 4) counts[(size_t)b * 4 + tid] = s[tid][0] + s[tid][1] + s[tid][2] + s[tid][3];
 }
 
-static bool raster_mesh_ok(const char* what, const char* name, const hoisdf_mesh* m, int B) {
-  if (!m) return true;
-  char label[64];
-  snprintf(label, sizeof label, "%s (%s)", what, name);
-  if (!mesh_shape_ok(label, B, m->V, m->max_faces)) return false;
-  if (m->face_batch_stride != 0 && m->face_batch_stride < 3L * m->max_faces) {
-    set_error("%s: %s face_batch_stride=%ld (0 or >= 3 max_faces)", what, name, m->face_batch_stride);
-    return false;
-  }
-  return true;
+// the workspace is one array of records: a Bump of one piece, so that it rounds as every other workspace does
+static long raster_workspace_bytes(long B, long nrec) {
+  Bump w(nullptr, 0);
+  w.take(B * nrec * (long)sizeof(RasterRec));
+  return w.bytes();
 }
 static RasterMesh raster_mesh(const hoisdf_mesh* m) {
   if (!m) return {nullptr, nullptr, nullptr, 0, 0, 0};
@@ -278,7 +273,7 @@ using namespace hoisdf;
 extern "C" long hoisdf_raster_workspace_bytes(int B, int hand_max_faces, int obj_max_faces) {
   if (!mesh_shape_ok("raster_workspace_bytes (hand)", B, 0, hand_max_faces) || !mesh_shape_ok("raster_workspace_bytes (obj)", B, 0, obj_max_faces))
     return -1;
-  return align256((long)B * ((long)hand_max_faces + obj_max_faces) * (long)sizeof(RasterRec));
+  return raster_workspace_bytes(B, (long)hand_max_faces + obj_max_faces);
 }
 
 extern "C" int hoisdf_raster_meshes(const hoisdf_mesh* hand, const hoisdf_mesh* obj, const float* K, int B, int width, int height,
@@ -286,7 +281,7 @@ extern "C" int hoisdf_raster_meshes(const hoisdf_mesh* hand, const hoisdf_mesh* 
                                     int hm_w, int hm_h, int32_t* counts, void* workspace, long workspace_bytes, void* stream) {
   HOISDF_REQUIRE(hand || obj, HOISDF_ERR_INVALID, "raster_meshes: null pointer (hand and obj: one mesh at least)");
   HOISDF_REQUIRE(B >= 0 && B <= 65535, HOISDF_ERR_INVALID, "raster_meshes: B=%d (0 .. 65535)", B);
-  if (!raster_mesh_ok("raster_meshes", "hand", hand, B) || !raster_mesh_ok("raster_meshes", "obj", obj, B)) return HOISDF_ERR_INVALID;
+  if (!mesh_desc_ok("raster_meshes", "hand", hand, B, true) || !mesh_desc_ok("raster_meshes", "obj", obj, B, true)) return HOISDF_ERR_INVALID;
   HOISDF_REQUIRE(width >= 1 && width <= HOISDF_RASTER_MAX_SIZE && height >= 1 && height <= HOISDF_RASTER_MAX_SIZE, HOISDF_ERR_INVALID,
                  "raster_meshes: width=%d height=%d (1 .. %d)", width, height, HOISDF_RASTER_MAX_SIZE);
   HOISDF_REQUIRE(half_pixel == 0 || half_pixel == 1, HOISDF_ERR_INVALID, "raster_meshes: half_pixel=%d (0 or 1)", half_pixel);
@@ -298,11 +293,9 @@ extern "C" int hoisdf_raster_meshes(const hoisdf_mesh* hand, const hoisdf_mesh* 
                    "raster_meshes: hm_w=%d hm_h=%d (>= 1, dividing width=%d and height=%d)", hm_w, hm_h, width, height);
   if (B == 0) return HOISDF_OK;
   HOISDF_REQUIRE(K, HOISDF_ERR_INVALID, "raster_meshes: null pointer (K)");
-  for (const hoisdf_mesh* m : {hand, obj})
-    HOISDF_REQUIRE(!m || (m->V > 0 && m->verts && (m->max_faces == 0 || m->faces)), HOISDF_ERR_INVALID,
-                   "raster_meshes: null pointer (verts, faces) or a mesh without vertices");
+  if (!mesh_data_ok("raster_meshes", "hand", hand) || !mesh_data_ok("raster_meshes", "obj", obj)) return HOISDF_ERR_INVALID;
   const long nrec = (long)(hand ? hand->max_faces : 0) + (obj ? obj->max_faces : 0);
-  const long need = align256((long)B * nrec * (long)sizeof(RasterRec));
+  const long need = raster_workspace_bytes(B, nrec);
   HOISDF_REQUIRE(workspace || need == 0, HOISDF_ERR_INVALID, "raster_meshes: null pointer (workspace)");
   HOISDF_REQUIRE(workspace_bytes >= need, HOISDF_ERR_INVALID, "raster_meshes: workspace of %ld bytes, %ld needed", workspace_bytes, need);
   RasterArgs a;

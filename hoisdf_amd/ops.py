@@ -128,6 +128,15 @@ def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _workspace(query: str, *dims_dev, least: int = 1):
+    """_workspace("hoisdf_xxx_workspace_bytes", *dims, dev) -> (uint8 scratch tensor of at least `least` bytes, the size to pass on)"""
+    *dims, dev = dims_dev
+    n = getattr(lib(), query)(*dims)
+    if n < 0:
+        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
+    return torch.empty(max(n, least), device=dev, dtype=torch.uint8), n
+
+
 def _chk(*ts):
     cur = None
     for t in ts:
@@ -1988,10 +1997,7 @@ def ik_mano(joints, betas, assets):
 # synchronises or reads a value back.
 # ---------------------------------------------------------------------------------------------
 def _eval_workspace(B: int, V: int, dev) -> torch.Tensor:
-    n = lib().hoisdf_eval_workspace_bytes(B, V)
-    if n < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    return torch.empty(n, device=dev, dtype=torch.uint8)
+    return _workspace("hoisdf_eval_workspace_bytes", B, V, dev, least=0)[0]
 
 
 def eval_thresholds(ths, dev) -> torch.Tensor:
@@ -2064,10 +2070,7 @@ def eval_mesh(pred, gt, thresholds, want_aligned: bool = False):
 
 def eval_accum_init(V: int, steps: int, dev) -> torch.Tensor:
     """a zeroed accumulator state (hoisdf_eval_accum_init) for V vertices and `steps` thresholds"""
-    n = lib().hoisdf_eval_accum_state_bytes(V, steps)
-    if n < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    state = torch.empty(n, device=dev, dtype=torch.uint8)
+    state = _workspace("hoisdf_eval_accum_state_bytes", V, steps, dev, least=0)[0]
     call("hoisdf_eval_accum_init", _p(state), V, steps, _st())
     return state
 
@@ -2461,31 +2464,50 @@ def encoder_infer(prepared: EncoderPrepared, img, want_aux: bool = True):
 # ---------------------------------------------------------------------------------------------
 # SDF supervision from meshes (csrc/mesh_sdf.hip, the hoisdf_mesh_* entries).  No gradient: these are labels.
 # ---------------------------------------------------------------------------------------------
-class PreparedMesh:
+def _counts(n, B: int, dev, what: str):
+    """per-sample counts -> int32 (B,) on the device (None stays None)"""
+    if n is None:
+        return None
+    n = torch.as_tensor(n).to(dev, torch.int32).contiguous()
+    if n.shape != (B,):
+        raise ValueError(f"{what} {tuple(n.shape)}: one count per sample ({B},)")
+    return n
+
+
+class _Mesh:
+    """A batch of meshes as the C ABI takes it: verts (B, V, 3) -> float32; faces (F, 3) shared by the batch or (B, F, 3) per sample,
+    any integer dtype -> int32; n_faces (B,) = the rows of each sample that count (None: all F) -> int32.  ``B`` given: the batch the
+    mesh must match; ``what`` opens the messages.  ``desc`` is the hoisdf_mesh; the tensors it points to live with this object."""
+
+    def __init__(self, verts, faces, n_faces, B: Optional[int], what: str):
+        verts = verts.detach().contiguous().float()
+        _chk(verts)
+        if verts.dim() != 3 or verts.shape[2] != 3 or (B is not None and verts.shape[0] != B):
+            raise ValueError(f"{what} vertices {tuple(verts.shape)}: one (V, 3) mesh per sample" + ("" if B is None else f" of {B}"))
+        dev, B = verts.device, verts.shape[0]
+        faces = faces.to(dev, torch.int32).contiguous()
+        if faces.dim() not in (2, 3) or faces.shape[-1] != 3 or (faces.dim() == 3 and faces.shape[0] != B):
+            raise ValueError(f"{what} faces {tuple(faces.shape)}: (F, 3) or ({B}, F, 3)")
+        self.verts, self.faces, self.n_faces = verts, faces, _counts(n_faces, B, dev, f"{what} face counts")
+        self.B, self.V, self.F = B, verts.shape[1], faces.shape[-2]
+        self.stride = 0 if faces.dim() == 2 else 3 * self.F
+        self.desc = _lib.Mesh(verts=verts.data_ptr(), faces=faces.data_ptr(), n_faces=None if self.n_faces is None else self.n_faces.data_ptr(),
+                              face_batch_stride=self.stride, V=self.V, max_faces=self.F)
+
+
+class PreparedMesh(_Mesh):
     """hoisdf_mesh_prepare on a batch of meshes: verts (B, V, 3); faces (F, 3) shared by the batch or (B, F, 3) per sample, any
     integer dtype; n_faces (B,) = the rows of each sample that count (None: all F).  Holds tris / area / cdf / box on the device."""
 
     def __init__(self, verts, faces, n_faces=None):
-        verts = verts.contiguous().float()
-        _chk(verts)
-        if verts.dim() != 3 or verts.shape[2] != 3 or faces.shape[-1] != 3 or faces.dim() not in (2, 3):
-            raise ValueError(f"mesh: verts {tuple(verts.shape)} (B, V, 3), faces {tuple(faces.shape)} (F, 3) or (B, F, 3)")
-        dev = verts.device
-        B, V, F = verts.shape[0], verts.shape[1], faces.shape[-2]
-        if faces.dim() == 3 and faces.shape[0] != B:
-            raise ValueError(f"mesh: {faces.shape[0]} face sets for {B} samples")
-        self.faces = faces.to(dev, torch.int32).contiguous()
-        self.n_faces = None if n_faces is None else torch.as_tensor(n_faces).to(dev, torch.int32).contiguous()
-        if self.n_faces is not None and self.n_faces.shape != (B,):
-            raise ValueError("mesh: one face count per sample")
-        self.B, self.V, self.F, self.verts = B, V, F, verts
-        self.stride = 0 if faces.dim() == 2 else 3 * F
+        super().__init__(verts, faces, n_faces, None, "mesh:")
+        B, F, dev = self.B, self.F, self.verts.device
         self.tris = torch.empty(B, F, 12, device=dev, dtype=torch.float32)
         self.area = torch.empty(B, F, device=dev, dtype=torch.float32)
         self.cdf = torch.empty(B, F, device=dev, dtype=torch.float32)
         self.box = torch.empty(B, 8, device=dev, dtype=torch.float32)
-        call("hoisdf_mesh_prepare", _p(verts), B, V, _p(self.faces), self.stride, _p(self.n_faces), F, _p(self.tris), _p(self.area),
-             _p(self.cdf), _p(self.box), _st())
+        call("hoisdf_mesh_prepare", _p(self.verts), B, self.V, _p(self.faces), self.stride, _p(self.n_faces), F, _p(self.tris),
+             _p(self.area), _p(self.cdf), _p(self.box), _st())
 
 
 def _as_prepared(verts, faces, n_faces) -> PreparedMesh:
@@ -2550,27 +2572,15 @@ def mesh_sdf_rows(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces, han
                   sigma=(0.01, 0.003), uniform_every: int = 16, pad: float = 0.05, clamp: float = 0.05, seed: int = 0):
     """hoisdf_mesh_sdf_rows: hand mesh (B, Vh, 3) with shared faces (Fh, 3), object mesh (B, Vo, 3) with faces (B, Fo, 3) (or
     shared (Fo, 3)) and face counts obj_n_faces (B,) or None -> rows (B, n_hand + n_obj, 6) = [x y z sdf_hand sdf_obj label]."""
-    hand_verts, obj_verts = hand_verts.contiguous().float(), obj_verts.contiguous().float()
-    _chk(hand_verts, obj_verts)
-    dev, B = hand_verts.device, hand_verts.shape[0]
-    if obj_verts.shape[0] != B or hand_verts.dim() != 3 or obj_verts.dim() != 3:
-        raise ValueError("mesh_sdf_rows: one hand and one object mesh per sample")
-    hf = hand_faces.to(dev, torch.int32).contiguous()
-    of = obj_faces.to(dev, torch.int32).contiguous()
-    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
+    mh = _Mesh(hand_verts, hand_faces, None, None, "mesh_sdf_rows: hand")
+    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "mesh_sdf_rows: object")
+    dev, B = mh.verts.device, mh.B
     lab = hand_vert_label.to(dev, torch.int32).contiguous()
-    if lab.shape != (hand_verts.shape[1],) or hf.dim() != 2 or (of.dim() == 3 and of.shape[0] != B) or (on is not None and on.shape != (B,)):
-        raise ValueError("mesh_sdf_rows: hand faces (Fh, 3), one label per hand vertex, object faces (Fo, 3) or (B, Fo, 3), counts (B,)")
-    Fh, Fo = hf.shape[0], of.shape[-2]
-    mh = _lib.Mesh(verts=hand_verts.data_ptr(), faces=hf.data_ptr(), n_faces=None, face_batch_stride=0, V=hand_verts.shape[1], max_faces=Fh)
-    mo = _lib.Mesh(verts=obj_verts.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
-                   face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=obj_verts.shape[1], max_faces=Fo)
-    nws = lib().hoisdf_mesh_sdf_rows_workspace_bytes(B, Fh, Fo)
-    if nws < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    if lab.shape != (mh.V,) or mh.faces.dim() != 2:
+        raise ValueError("mesh_sdf_rows: hand faces (Fh, 3) shared by the batch, one label per hand vertex")
+    ws, nws = _workspace("hoisdf_mesh_sdf_rows_workspace_bytes", B, mh.F, mo.F, dev)
     rows = torch.empty(B, n_hand + n_obj, 6, device=dev, dtype=torch.float32)
-    call("hoisdf_mesh_sdf_rows", C.addressof(mh), C.addressof(mo), _p(lab), B, n_hand, n_obj, float(sigma[0]), float(sigma[1]),
+    call("hoisdf_mesh_sdf_rows", C.addressof(mh.desc), C.addressof(mo.desc), _p(lab), B, n_hand, n_obj, float(sigma[0]), float(sigma[1]),
          int(uniform_every), float(pad), float(clamp), int(seed) & 0x7FFFFFFFFFFFFFFF, _p(rows), 6, _p(ws), nws, _st())
     return rows
 
@@ -2588,28 +2598,11 @@ def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=N
     grid float32 (B, 8) = lo xyz, cell xyz, the bits of n_x | n_y << 8 | n_z << 16, 0; with want_mask also inside uint8
     (B, 64^3): 1 where cell ix + n_x (iy + n_y iz) lies in both meshes, zero from n_x n_y n_z on.  want_mask may be that tensor:
     it is written in place, and its bytes from n_x n_y n_z on are left as they are."""
-    hand_verts, obj_verts = hand_verts.contiguous().float(), obj_verts.contiguous().float()
-    _chk(hand_verts, obj_verts)
-    if hand_verts.dim() != 3 or obj_verts.dim() != 3 or obj_verts.shape[0] != hand_verts.shape[0] or hand_verts.shape[2] != 3 or obj_verts.shape[2] != 3:
-        raise ValueError(f"eval_interaction: hand {tuple(hand_verts.shape)} and object {tuple(obj_verts.shape)}: one (V, 3) mesh of each per sample")
-    dev, B = hand_verts.device, hand_verts.shape[0]
-    hf = hand_faces.to(dev, torch.int32).contiguous()
-    of = obj_faces.to(dev, torch.int32).contiguous()
-    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
-    ov = None if obj_n_verts is None else torch.as_tensor(obj_n_verts).to(dev, torch.int32).contiguous()
-    hn = None if hand_n_faces is None else torch.as_tensor(hand_n_faces).to(dev, torch.int32).contiguous()
-    if any(f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) for f in (hf, of)) or any(
-            n is not None and n.shape != (B,) for n in (on, ov, hn)):
-        raise ValueError("eval_interaction: faces (F, 3) or (B, F, 3), counts (B,)")
-    Vh, Vo, Fh, Fo = hand_verts.shape[1], obj_verts.shape[1], hf.shape[-2], of.shape[-2]
-    mh = _lib.Mesh(verts=hand_verts.data_ptr(), faces=hf.data_ptr(), n_faces=None if hn is None else hn.data_ptr(),
-                   face_batch_stride=0 if hf.dim() == 2 else 3 * Fh, V=Vh, max_faces=Fh)
-    mo = _lib.Mesh(verts=obj_verts.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
-                   face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=Vo, max_faces=Fo)
-    nws = lib().hoisdf_eval_interaction_workspace_bytes(B, Vh, Fh, Vo, Fo)
-    if nws < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    mh = _Mesh(hand_verts, hand_faces, hand_n_faces, None, "eval_interaction: hand")
+    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "eval_interaction: object")
+    dev, B = mh.verts.device, mh.B
+    ov = _counts(obj_n_verts, B, dev, "eval_interaction: obj_n_verts")
+    ws, nws = _workspace("hoisdf_eval_interaction_workspace_bytes", B, mh.V, mh.F, mo.V, mo.F, dev)
     f32 = dict(device=dev, dtype=torch.float32)
     i32 = dict(device=dev, dtype=torch.int32)
     out = {"pen_hand": torch.empty(B, **f32), "pen_obj": torch.empty(B, **f32), "min_dist": torch.empty(B, **f32),
@@ -2623,7 +2616,7 @@ def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=N
             raise ValueError(f"eval_interaction: the mask must be a contiguous uint8 tensor of shape ({B}, {cells}) on {dev}")
     elif want_mask:
         mask = torch.zeros(B, cells, device=dev, dtype=torch.uint8)
-    call("hoisdf_eval_interaction", C.addressof(mh), C.addressof(mo), _p(ov), B, float(contact_dist), float(voxel), _p(out["pen_hand"]),
+    call("hoisdf_eval_interaction", C.addressof(mh.desc), C.addressof(mo.desc), _p(ov), B, float(contact_dist), float(voxel), _p(out["pen_hand"]),
          _p(out["pen_obj"]), _p(out["min_dist"]), _p(out["contact_verts"]), _p(out["in_contact"]), _p(out["volume"]),
          _p(out["inside_count"]), _p(mask), _p(out["grid"]), _p(ws), nws, _st())
     if mask is not None:
@@ -2647,37 +2640,29 @@ def _loss_weight(w, B: int, V: int, dev, what: str):
 
 class _InteractionLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hand_verts, obj_verts, hf, of, hn, on, ov, weights, alpha):
-        hv, obv = hand_verts.detach().contiguous().float(), obj_verts.detach().contiguous().float()
-        _chk(hv, obv)
-        dev, B = hv.device, hv.shape[0]
-        Vh, Vo, Fh, Fo = hv.shape[1], obv.shape[1], hf.shape[-2], of.shape[-2]
-        mh = _lib.Mesh(verts=hv.data_ptr(), faces=hf.data_ptr(), n_faces=None if hn is None else hn.data_ptr(),
-                       face_batch_stride=0 if hf.dim() == 2 else 3 * Fh, V=Vh, max_faces=Fh)
-        mo = _lib.Mesh(verts=obv.data_ptr(), faces=of.data_ptr(), n_faces=None if on is None else on.data_ptr(),
-                       face_batch_stride=0 if of.dim() == 2 else 3 * Fo, V=Vo, max_faces=Fo)
-        nws = lib().hoisdf_interaction_loss_workspace_bytes(B, Vh, Fh, Vo, Fo)
-        if nws < 0:
-            raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-        ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    def forward(ctx, hand_verts, obj_verts, mh, mo, ov, weights, alpha):
+        # mh / mo: the two meshes marshalled from (detached copies of) hand_verts / obj_verts, which are here for the graph alone
+        dev, B = mh.verts.device, mh.B
+        ws, nws = _workspace("hoisdf_interaction_loss_workspace_bytes", B, mh.V, mh.F, mo.V, mo.F, dev)
         out = [torch.empty(B, device=dev, dtype=torch.float32) for _ in range(3)]
         (wr, sr), (wa, sa), (wo, so) = weights
-        common = (C.addressof(mh), C.addressof(mo), _p(ov), B, _p(wr), sr, _p(wa), sa, _p(wo), so, float(alpha))
+        common = (C.addressof(mh.desc), C.addressof(mo.desc), _p(ov), B, _p(wr), sr, _p(wa), sa, _p(wo), so, float(alpha))
         call("hoisdf_interaction_loss_fwd", *common, _p(out[0]), _p(out[1]), _p(out[2]), _p(ws), nws, _st())
-        # the backward reads the workspace and every input again: all of them stay alive, and unchanged, with the context
-        ctx.keep = (hv, obv, hf, of, hn, on, ov, wr, wa, wo, mh, mo, ws)
+        # the backward reads the workspace and every input again: all of them (the meshes hold the tensors their descriptors point
+        # to) stay alive, and unchanged, with the context
+        ctx.keep = (mh, mo, ov, wr, wa, wo, ws)
         ctx.common, ctx.nws = common, nws
         ctx.set_materialize_grads(False)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, g_rep_hand, g_att, g_rep_obj):
-        hv, obv = ctx.keep[0], ctx.keep[1]
+        mh, mo = ctx.keep[0], ctx.keep[1]
         gs = [None if g is None else g.contiguous().float() for g in (g_rep_hand, g_att, g_rep_obj)]
         _chk(*gs)
-        d_hand, d_obj = torch.empty_like(hv), torch.empty_like(obv)
+        d_hand, d_obj = torch.empty_like(mh.verts), torch.empty_like(mo.verts)
         call("hoisdf_interaction_loss_bwd", *ctx.common, _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(d_hand), _p(d_obj), _p(ctx.keep[-1]), ctx.nws, _st())
-        return d_hand, d_obj, None, None, None, None, None, None, None
+        return d_hand, d_obj, None, None, None, None, None
 
 
 def interaction_loss(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=None, obj_n_verts=None, rep_w_hand=None,
@@ -2687,22 +2672,14 @@ def interaction_loss(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=N
     saturates -> (rep_hand, att, rep_obj), each (B,): the weighted means of max(0, -sdf_obj) and alpha tanh(max(0, sdf_obj) / alpha)
     over the hand vertices and of max(0, -sdf_hand) over the object's vertices that count.  Gradients flow to hand_verts and obj_verts
     only (the envelope rule of include/hoisdf.h "interaction loss"); order-fixed: two calls give the same bits."""
-    if hand_verts.dim() != 3 or obj_verts.dim() != 3 or obj_verts.shape[0] != hand_verts.shape[0] or hand_verts.shape[2] != 3 or obj_verts.shape[2] != 3:
-        raise ValueError(f"interaction_loss: hand {tuple(hand_verts.shape)} and object {tuple(obj_verts.shape)}: one (V, 3) mesh of each per sample")
-    _chk(hand_verts, obj_verts)
-    dev, B = hand_verts.device, hand_verts.shape[0]
-    hf = hand_faces.to(dev, torch.int32).contiguous()
-    of = obj_faces.to(dev, torch.int32).contiguous()
-    on = None if obj_n_faces is None else torch.as_tensor(obj_n_faces).to(dev, torch.int32).contiguous()
-    ov = None if obj_n_verts is None else torch.as_tensor(obj_n_verts).to(dev, torch.int32).contiguous()
-    hn = None if hand_n_faces is None else torch.as_tensor(hand_n_faces).to(dev, torch.int32).contiguous()
-    if any(f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) for f in (hf, of)) or any(
-            n is not None and n.shape != (B,) for n in (on, ov, hn)):
-        raise ValueError("interaction_loss: faces (F, 3) or (B, F, 3), counts (B,)")
-    Vh, Vo = hand_verts.shape[1], obj_verts.shape[1]
-    weights = (_loss_weight(rep_w_hand, B, Vh, dev, "rep_w_hand"), _loss_weight(att_w_hand, B, Vh, dev, "att_w_hand"),
-               _loss_weight(rep_w_obj, B, Vo, dev, "rep_w_obj"))
-    return _InteractionLoss.apply(hand_verts, obj_verts, hf, of, hn, on, ov, weights, float(alpha))
+    mh = _Mesh(hand_verts, hand_faces, hand_n_faces, None, "interaction_loss: hand")
+    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "interaction_loss: object")
+    _chk(hand_verts, obj_verts)                              # the gradients go back as float32: no other dtype is taken
+    dev, B = mh.verts.device, mh.B
+    ov = _counts(obj_n_verts, B, dev, "interaction_loss: obj_n_verts")
+    weights = (_loss_weight(rep_w_hand, B, mh.V, dev, "rep_w_hand"), _loss_weight(att_w_hand, B, mh.V, dev, "att_w_hand"),
+               _loss_weight(rep_w_obj, B, mo.V, dev, "rep_w_obj"))
+    return _InteractionLoss.apply(hand_verts, obj_verts, mh, mo, ov, weights, float(alpha))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2765,11 +2742,8 @@ def iso_surface(values, grid, n: int, iso: float = 0.0, max_verts: Optional[int]
         shift = torch.zeros(B, 3, device=dev, dtype=torch.float32) if out_shift is None else out_shift.reshape(B, 3).contiguous().float()
         _chk(shift)
     scale = 1.0 if out_scale is None else float(out_scale)
-    nws = lib().hoisdf_iso_extract_workspace_bytes(B, int(n))
-    if nws < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
-    nv = torch.zeros(B, device=dev, dtype=torch.int32)
+    ws, nws = _workspace("hoisdf_iso_extract_workspace_bytes", B, int(n), dev)
+    nv =torch.zeros(B, device=dev, dtype=torch.int32)
     nf = torch.zeros(B, device=dev, dtype=torch.int32)
 
     def run(verts, faces, mv, mf):
@@ -2794,28 +2768,19 @@ def eval_surface(pred_verts, pred_n_verts, gt_verts, gt_faces, gt_n_faces=None, 
     gt_faces (F, 3) shared or (B, F, 3) with counts gt_n_faces -> a dict of (B,) tensors: pred_to_gt, gt_to_pred, chamfer (mean
     squared distances, square metres) and n_used int32 (0: the sample has no predicted vertex or no usable face, and zeros).
     With extras also samples (B, n_samples, 3), the points drawn on the ground-truth surface, and nearest (B, n_samples) int32."""
-    pred_verts, gt_verts = pred_verts.contiguous().float(), gt_verts.contiguous().float()
-    _chk(pred_verts, gt_verts)
-    if pred_verts.dim() != 3 or gt_verts.dim() != 3 or pred_verts.shape[2] != 3 or gt_verts.shape[2] != 3 or gt_verts.shape[0] != pred_verts.shape[0]:
-        raise ValueError(f"eval_surface: predicted {tuple(pred_verts.shape)} and ground truth {tuple(gt_verts.shape)}: (B, ., 3) each")
+    pred_verts = pred_verts.contiguous().float()
+    _chk(pred_verts)
+    if pred_verts.dim() != 3 or pred_verts.shape[2] != 3:
+        raise ValueError(f"eval_surface: predicted {tuple(pred_verts.shape)}: (B, max_verts, 3)")
     dev, B, mv = pred_verts.device, pred_verts.shape[0], pred_verts.shape[1]
-    pn = torch.as_tensor(pred_n_verts).to(dev, torch.int32).contiguous()
-    gf = gt_faces.to(dev, torch.int32).contiguous()
-    gn = None if gt_n_faces is None else torch.as_tensor(gt_n_faces).to(dev, torch.int32).contiguous()
-    if pn.shape != (B,) or gf.dim() not in (2, 3) or gf.shape[-1] != 3 or (gf.dim() == 3 and gf.shape[0] != B) or (gn is not None and gn.shape != (B,)):
-        raise ValueError("eval_surface: counts (B,), faces (F, 3) or (B, F, 3)")
-    F = gf.shape[-2]
-    m = _lib.Mesh(verts=gt_verts.data_ptr(), faces=gf.data_ptr(), n_faces=None if gn is None else gn.data_ptr(),
-                  face_batch_stride=0 if gf.dim() == 2 else 3 * F, V=gt_verts.shape[1], max_faces=F)
-    nws = lib().hoisdf_eval_surface_workspace_bytes(B, mv, F, int(n_samples))
-    if nws < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
-    out = {"pred_to_gt": torch.empty(B, device=dev, dtype=torch.float32), "gt_to_pred": torch.empty(B, device=dev, dtype=torch.float32),
+    m = _Mesh(gt_verts, gt_faces, gt_n_faces, B, "eval_surface: ground-truth")
+    pn = _counts(pred_n_verts, B, dev, "eval_surface: pred_n_verts")
+    ws, nws = _workspace("hoisdf_eval_surface_workspace_bytes", B, mv, m.F, int(n_samples), dev)
+    out ={"pred_to_gt": torch.empty(B, device=dev, dtype=torch.float32), "gt_to_pred": torch.empty(B, device=dev, dtype=torch.float32),
            "chamfer": torch.empty(B, device=dev, dtype=torch.float32), "n_used": torch.empty(B, device=dev, dtype=torch.int32)}
     samples = torch.empty(B, int(n_samples), 3, device=dev, dtype=torch.float32) if extras else None
     nearest = torch.empty(B, int(n_samples), device=dev, dtype=torch.int32) if extras else None
-    call("hoisdf_eval_surface", _p(pred_verts), _p(pn), mv, C.addressof(m), B, int(n_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
+    call("hoisdf_eval_surface", _p(pred_verts), _p(pn), mv, C.addressof(m.desc), B, int(n_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
          _p(out["pred_to_gt"]), _p(out["gt_to_pred"]), _p(out["chamfer"]), _p(out["n_used"]), _p(samples), _p(nearest), _p(ws), nws, _st())
     if extras:
         out["samples"], out["nearest"] = samples, nearest
@@ -2825,25 +2790,6 @@ def eval_surface(pred_verts, pred_n_verts, gt_verts, gt_faces, gt_n_faces=None, 
 # ---------------------------------------------------------------------------------------------
 # Mesh rasteriser (csrc/raster.hip: hoisdf_raster_meshes, hoisdf_raster_overlay, hoisdf_eval_silhouette).  No gradient.
 # ---------------------------------------------------------------------------------------------
-def _raster_mesh(verts, faces, n_faces, B: Optional[int], what: str):
-    """-> (hoisdf_mesh or None, the tensors it points to, B, max_faces)"""
-    if verts is None:
-        return None, (), B, 0
-    verts = verts.contiguous().float()
-    _chk(verts)
-    if verts.dim() != 3 or verts.shape[2] != 3 or (B is not None and verts.shape[0] != B):
-        raise ValueError(f"raster_meshes: {what} vertices {tuple(verts.shape)}: one (V, 3) mesh per sample")
-    dev, B = verts.device, verts.shape[0]
-    f = faces.to(dev, torch.int32).contiguous()
-    n = None if n_faces is None else torch.as_tensor(n_faces).to(dev, torch.int32).contiguous()
-    if f.dim() not in (2, 3) or f.shape[-1] != 3 or (f.dim() == 3 and f.shape[0] != B) or (n is not None and n.shape != (B,)):
-        raise ValueError(f"raster_meshes: {what} faces (F, 3) or (B, F, 3), counts (B,)")
-    F = f.shape[-2]
-    m = _lib.Mesh(verts=verts.data_ptr(), faces=f.data_ptr(), n_faces=None if n is None else n.data_ptr(),
-                  face_batch_stride=0 if f.dim() == 2 else 3 * F, V=verts.shape[1], max_faces=F)
-    return m, (verts, f, n), B, F
-
-
 @torch.no_grad()
 def raster_meshes(hand_verts, hand_faces, obj_verts, obj_faces, K, width: int, height: int, hand_n_faces=None, obj_n_faces=None,
                   half_pixel: bool = False, near: float = 0.01, hm_shape=None, want=("ids", "depth", "counts"), out=None):
@@ -2854,9 +2800,9 @@ def raster_meshes(hand_verts, hand_faces, obj_verts, obj_faces, K, width: int, h
     the modal masks under the NEAREST fold of image_crop.  `out`: a dict of tensors to write into instead of new ones."""
     if hand_verts is None and obj_verts is None:
         raise ValueError("raster_meshes: one mesh at least")
-    mh, keep_h, B, Fh = _raster_mesh(hand_verts, hand_faces, hand_n_faces, None, "hand")
-    mo, keep_o, B, Fo = _raster_mesh(obj_verts, obj_faces, obj_n_faces, B, "object")
-    dev = (keep_h or keep_o)[0].device
+    mh = None if hand_verts is None else _Mesh(hand_verts, hand_faces, hand_n_faces, None, "raster_meshes: hand")
+    mo = None if obj_verts is None else _Mesh(obj_verts, obj_faces, obj_n_faces, mh and mh.B, "raster_meshes: object")
+    dev, B = (mh or mo).verts.device, (mh or mo).B
     K = K.to(dev).float().reshape(B, 6).contiguous()
     _chk(K)
     names = list(want) + (["hand_seg", "obj_seg"] if hm_shape is not None else [])
@@ -2873,12 +2819,9 @@ def raster_meshes(hand_verts, hand_faces, obj_verts, obj_faces, K, width: int, h
         elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"raster_meshes: out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
         res[k] = t
-    nws = lib().hoisdf_raster_workspace_bytes(B, Fh, Fo)
-    if nws < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    ws, nws = _workspace("hoisdf_raster_workspace_bytes", B, mh.F if mh else 0, mo.F if mo else 0, dev)
     hm_h, hm_w = (int(hm_shape[0]), int(hm_shape[1])) if hm_shape is not None else (0, 0)
-    call("hoisdf_raster_meshes", None if mh is None else C.addressof(mh), None if mo is None else C.addressof(mo), _p(K), B, int(width),
+    call("hoisdf_raster_meshes", mh and C.addressof(mh.desc), mo and C.addressof(mo.desc), _p(K), B, int(width),
          int(height), int(bool(half_pixel)), float(near), _p(res.get("ids")), _p(res.get("depth")), _p(res.get("hand_seg")),
          _p(res.get("obj_seg")), hm_w, hm_h, _p(res.get("counts")), _p(ws), nws, _st())
     return res
