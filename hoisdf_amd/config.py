@@ -84,6 +84,17 @@ class Config:
     interaction_rep_weight = 100.0
     interaction_att_weight = 10.0
     interaction_alpha = 0.01             # metres
+    # not in the reference: training holds the PREDICTED hand mesh and the PREDICTED object (posed as for the interaction loss) to
+    # the mask targets hand_seg / obj_seg, which otherwise supervise only the CNN decoder: loss["silhouette_in"] = the projected
+    # vertices' distance to hand_seg OR obj_seg (the bilinear read of the masks' exact distance transform; the masks are modal, so
+    # the union is what a vertex may hide behind), loss["silhouette_cover"] = the distance of every pixel of a mesh's own mask to its
+    # nearest projected vertex; hand plus object, in mask pixels divided by the mask width (hoisdf_mask_edt,
+    # hoisdf_silhouette_loss_fwd / _bwd, csrc/silhouette_loss.hip).  Also HOISDF_SILHOUETTE_LOSS=1.  Needs meta_info["obj_cls"]
+    # and the templates as meshes, like the interaction loss; not offered for the IK variant.  The two weights are UNTUNED
+    # starting values (no dataset and no trained weights here to tune them on)
+    silhouette_loss = False
+    silhouette_in_weight = 10.0
+    silhouette_cover_weight = 10.0
     # not in the reference: the eval forward also extracts the zero level set of the two learned fields as triangle meshes
     # (Model.field_surface: hoisdf_iso_extract, csrc/isosurf.hip) and test.py's Evaluator reports their Chamfer distance to the
     # ground-truth MANO mesh and to the posed ground-truth template in a block appended to results.txt.  Also HOISDF_FIELD=1 /

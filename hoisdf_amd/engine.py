@@ -37,7 +37,9 @@ LOSS_WEIGHTS = {  # main/train.py:115-127 <- cfg attribute
     "obj_trans": "obj_trans_weight", "loss_joint_3d": "joint_weight", "loss_joint_cls": "cls_weight",
     "loss_all_joint_3d": "joint_weight",
     # not in the reference: the hand-object interaction loss (cfg.interaction_loss)
-    "interaction_rep": "interaction_rep_weight", "interaction_att": "interaction_att_weight"}
+    "interaction_rep": "interaction_rep_weight", "interaction_att": "interaction_att_weight",
+    # not in the reference: the silhouette loss of the predicted pair against the mask targets (cfg.silhouette_loss)
+    "silhouette_in": "silhouette_in_weight", "silhouette_cover": "silhouette_cover_weight"}
 
 
 def _mix_seed(epoch_seed: int, draw: int) -> int:
@@ -300,7 +302,9 @@ class Trainer:
                     src = MeshSdfSource(head.mano_layer if head is not None else self.model.ik_mano_layer, procedural_templates(), cfg)
                 self.seg_source = MeshSegSource(src, cfg)
         self.interaction_source = None
-        if self.model.interaction_loss_enabled():       # cfg.interaction_loss / HOISDF_INTERACTION_LOSS=1: the meshes of the existing source, else the same stand-ins
+        # cfg.interaction_loss / HOISDF_INTERACTION_LOSS=1, cfg.silhouette_loss / HOISDF_SILHOUETTE_LOSS=1 (both pose the predicted
+        # pair from the same templates): the meshes of the existing source, else the same stand-ins
+        if self.model.interaction_loss_enabled() or self.model.silhouette_loss_enabled():
             src = self.sdf_source if self.sdf_source is not None else getattr(self.seg_source, "source", None)
             if src is None:
                 from .sdf_data import MeshSdfSource, procedural_templates

@@ -165,6 +165,8 @@ class Model(nn.Module):
         self.set_interaction_source(None)
         if cfg.use_inverse_kinematics and self.interaction_loss_enabled():
             raise ValueError("cfg.interaction_loss needs the predicted hand mesh in training: the IK variant (cfg.use_inverse_kinematics) has none")
+        if cfg.use_inverse_kinematics and self.silhouette_loss_enabled():
+            raise ValueError("cfg.silhouette_loss needs the predicted hand mesh in training: the IK variant (cfg.use_inverse_kinematics) has none")
 
     def set_ik_mano_layer(self, mano_layer):
         object.__setattr__(self, "ik_mano_layer", mano_layer)
@@ -173,8 +175,12 @@ class Model(nn.Module):
         """cfg.interaction_loss (default False) or HOISDF_INTERACTION_LOSS=1: training adds interaction_rep / interaction_att"""
         return bool(getattr(self.cfg, "interaction_loss", False)) or os.environ.get("HOISDF_INTERACTION_LOSS", "") == "1"
 
+    def silhouette_loss_enabled(self) -> bool:
+        """cfg.silhouette_loss (default False) or HOISDF_SILHOUETTE_LOSS=1: training adds silhouette_in / silhouette_cover"""
+        return bool(getattr(self.cfg, "silhouette_loss", False)) or os.environ.get("HOISDF_SILHOUETTE_LOSS", "") == "1"
+
     def set_interaction_source(self, source, att_w_hand=None, rep_w_hand=None, rep_w_obj=None):
-        """the meshes of the interaction loss: a ``sdf_data.MeshSdfSource`` (object templates + the MANO layer's faces; the Trainer
+        """the meshes of the interaction loss (and of the silhouette loss, which poses the same pair): a ``sdf_data.MeshSdfSource`` (object templates + the MANO layer's faces; the Trainer
         hands its own over) and the per-vertex weights - ``att_w_hand`` (778,) defaults to sdf_data.contact_zone_weights of the
         source's layer, the two repulsion weights to ones.  A plain attribute, no submodule: the checkpoint schema stays as it is"""
         if source is not None and att_w_hand is None:
@@ -182,17 +188,18 @@ class Model(nn.Module):
             att_w_hand = contact_zone_weights(source.layer.th_weights)
         object.__setattr__(self, "_interaction", None if source is None else (source, att_w_hand, rep_w_hand, rep_w_obj))
 
-    def _interaction_losses(self, hand_rel, obj_rot, obj_trans, meta_info, loss):
-        """The predicted hand against the predicted object (hoisdf_interaction_loss_fwd / _bwd): loss["interaction_rep"] = the
-        repulsion of both directions, loss["interaction_att"] = the attraction of the hand's contact zones, each (B,).  The object
-        is posed in torch from the mean votes, so autograd carries the vertex gradient on to both vote heads; a sample without an
-        evaluated object (obj_cls < 0) has face and vertex count 0 and adds 0."""
+    def _predicted_pair(self, hand_rel, obj_rot, obj_trans, meta_info, what):
+        """The PREDICTED pair of a training step in the camera frame, the one place where the mesh losses pose it: hand = the MANO
+        mesh + mano_root, object = the template obj_cls turned and moved in torch by the mean votes + obj_center_cam, so autograd
+        carries a vertex gradient on to both vote heads.  -> hand (B, 778, 3), obj (B, V, 3), the packed templates gathered per
+        sample (faces, n_faces, n_verts), used (B,) bool: obj_cls >= 0 (a sample that is not used borrows template 0: give it
+        the counts 0)"""
         if self._interaction is None:
-            raise RuntimeError("cfg.interaction_loss needs the meshes: Model.set_interaction_source(MeshSdfSource) (the Trainer does it)")
+            raise RuntimeError(f"cfg.{what} needs the meshes: Model.set_interaction_source(MeshSdfSource) (the Trainer does it)")
         if "obj_cls" not in meta_info:
-            raise KeyError("cfg.interaction_loss needs meta_info['obj_cls']: the object template of every sample (-1: none)")
+            raise KeyError(f"cfg.{what} needs meta_info['obj_cls']: the object template of every sample (-1: none)")
         from .metrics import batch_rodrigues
-        src, att_w, rep_wh, rep_wo = self._interaction
+        src = self._interaction[0]
         dev = hand_rel.device
         tm = src.to(dev).templates
         cls = meta_info["obj_cls"].to(dev).long().view(-1)
@@ -201,11 +208,39 @@ class Model(nn.Module):
         R = batch_rodrigues(obj_rot[-1].mean(1))
         obj = tm["verts"][k] @ R.transpose(1, 2) + (obj_trans[-1].mean(1) + meta_info["obj_center_cam"])[:, None]
         zero = torch.zeros_like(tm["n_faces"][k])
+        return hand, obj, tm["faces"][k], torch.where(used, tm["n_faces"][k], zero), torch.where(used, tm["n_verts"][k], zero), used
+
+    def _interaction_losses(self, hand_rel, obj_rot, obj_trans, meta_info, loss):
+        """The predicted hand against the predicted object (hoisdf_interaction_loss_fwd / _bwd): loss["interaction_rep"] = the
+        repulsion of both directions, loss["interaction_att"] = the attraction of the hand's contact zones, each (B,).  The object
+        is posed in torch from the mean votes, so autograd carries the vertex gradient on to both vote heads; a sample without an
+        evaluated object (obj_cls < 0) has face and vertex count 0 and adds 0."""
+        hand, obj, obj_faces, obj_nf, obj_nv, _ = self._predicted_pair(hand_rel, obj_rot, obj_trans, meta_info, "interaction_loss")
+        src, att_w, rep_wh, rep_wo = self._interaction
         rep_hand, att, rep_obj = ops.interaction_loss(
-            hand, src.layer.th_faces, obj, tm["faces"][k], torch.where(used, tm["n_faces"][k], zero), torch.where(used, tm["n_verts"][k], zero),
+            hand, src.layer.th_faces, obj, obj_faces, obj_nf, obj_nv,
             rep_wh, att_w, rep_wo, float(self.cfg.interaction_alpha))
         loss["interaction_rep"] = rep_hand + rep_obj
         loss["interaction_att"] = att
+
+    def _silhouette_losses(self, hand_rel, obj_rot, obj_trans, targets, meta_info, loss):
+        """The predicted pair against the mask targets (hoisdf_mask_edt, hoisdf_silhouette_loss_fwd / _bwd, once per mesh):
+        loss["silhouette_in"] = how far the projected vertices lie outside hand_seg OR obj_seg (the masks are modal: a hand vertex
+        hidden behind the object is no error), loss["silhouette_cover"] = how far the pixels of each mesh's own mask lie from its
+        nearest projected vertex; each (B,), the hand's plus the object's, in mask pixels divided by the mask width.  A sample
+        without an evaluated object (obj_cls < 0) has object vertex count 0 and adds the hand's share alone."""
+        from .render import mask_camera_rows
+        hand, obj, _, _, obj_nv, _ = self._predicted_pair(hand_rel, obj_rot, obj_trans, meta_info, "silhouette_loss")
+        B = hand.shape[0]
+        hand_seg, obj_seg = (targets[k].reshape(B, *targets[k].shape[-2:]) for k in ("hand_seg", "obj_seg"))
+        K = mask_camera_rows(meta_info["cam_intr"].to(hand.device), self.cfg)
+        allow = ops.mask_edt(hand_seg, obj_seg)
+        near = float(self.cfg.raster_near)
+        in_h, cov_h = ops.silhouette_loss(hand, K, allow, hand_seg, near=near)
+        in_o, cov_o = ops.silhouette_loss(obj, K, allow, obj_seg, n_verts=obj_nv, near=near)
+        width = float(hand_seg.shape[-1])
+        loss["silhouette_in"] = (in_h + in_o) / width
+        loss["silhouette_cover"] = (cov_h + cov_o) / width
 
     def _ik_layer(self, device):
         """the IK solve's layer on ``device``: as no submodule it does not follow Model.to, so the first native call moves it (once)"""
@@ -592,6 +627,8 @@ class Model(nn.Module):
             self._mano_and_object_pose(hs, obj_rot, obj_trans, targets, training, loss, out)
             if training and self.interaction_loss_enabled():
                 self._interaction_losses(out["mano_mesh_out"], obj_rot, obj_trans, meta_info, loss)
+            if training and self.silhouette_loss_enabled():
+                self._silhouette_losses(out["mano_mesh_out"], obj_rot, obj_trans, targets, meta_info, loss)
             side_made = [t for t in list(loss.values()) + list(out.values()) if torch.is_tensor(t)]
         self._hand_votes(hand_rel, hand_enc, targets, training, loss, out)             # ---- (ambient stream)
         plan.join(*side_made)

@@ -2860,3 +2860,96 @@ def eval_silhouette(pred_hand, pred_obj, gt_hand, gt_obj):
     counts = torch.empty(B, 4, device=masks[0].device, dtype=torch.int32)
     call("hoisdf_eval_silhouette", *[_p(m) for m in masks], B, masks[0].shape[1], _p(counts), _st())
     return counts
+
+
+# ---------------------------------------------------------------------------------------------
+# Silhouette loss (csrc/silhouette_loss.hip: hoisdf_mask_edt, hoisdf_silhouette_loss_fwd / _bwd): a mask's exact distance transform,
+# and one projected point set held to a pair of mask maps, with the gradient to the points.
+# ---------------------------------------------------------------------------------------------
+def _mask_maps(what: str, *masks):
+    """float masks (B, h, w) of one shape (None stays None) -> contiguous float32 tensors, B, h, w"""
+    ms = [None if m is None else m.detach().float().contiguous() for m in masks]
+    _chk(*ms)
+    first = next(m for m in ms if m is not None)
+    if first.dim() != 3 or any(m is not None and m.shape != first.shape for m in ms):
+        raise ValueError(f"{what}: masks of one shape (B, h, w), got {[None if m is None else tuple(m.shape) for m in ms]}")
+    return ms, first.shape[0], first.shape[1], first.shape[2]
+
+
+@torch.no_grad()
+def mask_edt(mask, mask_or=None, want_nearest: bool = False):
+    """hoisdf_mask_edt: mask (B, h, w) float32, set where > 0.5 (with mask_or: the union of the two) -> d2 int32 (B, h, w): the exact
+    squared distance in pixels^2 to the nearest set pixel (0 at a set pixel, EDT_NONE = 2^30 in a sample without one); with
+    want_nearest also nearest int32 (B, h, w): the index y' w + x' of a nearest set pixel, the lowest on a tie (-1 without one)."""
+    if mask is None:
+        raise ValueError("mask_edt: a mask")
+    (mask, mask_or), B, h, w = _mask_maps("mask_edt", mask, mask_or)
+    d2 = torch.empty(B, h, w, device=mask.device, dtype=torch.int32)
+    nearest = torch.empty_like(d2) if want_nearest else None
+    call("hoisdf_mask_edt", _p(mask), _p(mask_or), B, w, h, _p(d2), _p(nearest), _st())
+    return (d2, nearest) if want_nearest else d2
+
+
+def silhouette_workspace_views(ws, B: int, V: int, h: int, w: int):
+    """the pieces of a hoisdf_silhouette_loss_fwd workspace (the layout include/hoisdf.h states: each piece rounded up to 256
+    bytes) as tensors over it -> dict: u, v float64 (B, V), cell int32 (B, V), nearest int32 (B, h, w), den float64 (B, 2)"""
+    up = lambda n: (n + 255) // 256 * 256
+    out, off = {}, 0
+    for name, dtype, shape in (("u", torch.float64, (B, V)), ("v", torch.float64, (B, V)), ("cell", torch.int32, (B, V)),
+                               ("nearest", torch.int32, (B, h, w)), ("den", torch.float64, (B, 2))):
+        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        out[name] = ws[off:off + n].view(dtype).view(shape)
+        off += up(n)
+    return out
+
+
+class _SilhouetteLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, K, allow_d2, cover, nv, weight, stride, near):
+        dev, (B, V, _) = verts.device, verts.shape
+        h, w = cover.shape[1:]
+        v = verts.detach().contiguous()
+        ws, nws = _workspace("hoisdf_silhouette_loss_workspace_bytes", B, V, w, h, dev)
+        inside, cov = torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32)
+        common = (_p(v), _p(nv), V, _p(K), B, _p(allow_d2), _p(cover), w, h, float(near), _p(weight), stride)
+        call("hoisdf_silhouette_loss_fwd", *common, _p(inside), _p(cov), _p(ws), nws, _st())
+        # the backward reads the workspace and every input again: they stay alive, and unchanged, with the context
+        ctx.keep = (v, nv, K, allow_d2, cover, weight, ws)
+        ctx.common, ctx.nws = common, nws
+        ctx.set_materialize_grads(False)
+        return inside, cov
+
+    @staticmethod
+    def backward(ctx, g_inside, g_cover):
+        gs = [None if g is None else g.contiguous().float() for g in (g_inside, g_cover)]
+        _chk(*gs)
+        d_verts = torch.empty_like(ctx.keep[0])
+        call("hoisdf_silhouette_loss_bwd", *ctx.common, _p(gs[0]), _p(gs[1]), _p(d_verts), _p(ctx.keep[-1]), ctx.nws, _st())
+        return d_verts, None, None, None, None, None, None, None
+
+
+def silhouette_loss(verts, K, allow_d2, cover, n_verts=None, weight=None, near: float = 0.01):
+    """hoisdf_silhouette_loss_fwd / _bwd: verts (B, V, 3) camera frame, metres; K (B, 6) or (B, 2, 3) FOR THE MASK GRID (mask pixel
+    (px, py) sits at (px, py): render.mask_camera_rows); allow_d2 int32 (B, h, w) of ``mask_edt``: where the projected vertices may
+    lie; cover float32 (B, h, w), set where > 0.5: the pixels that want a projected vertex near them; n_verts (B,) or None: rows
+    from there on are padding; weight (V,) or (B, V) or None = ones -> (inside, cover), each (B,), in mask pixels: the weighted mean
+    over the vertices of the bilinear read of sqrt(allow_d2) plus the distance back onto the map, and the mean over cover's set
+    pixels of the distance to the nearest projected vertex.  The gradient flows to verts only; order-fixed: two calls give the
+    same bits."""
+    if verts.dim() != 3 or verts.shape[2] != 3:
+        raise ValueError(f"silhouette_loss: verts {tuple(verts.shape)} must be (B, V, 3)")
+    _chk(verts)
+    dev, (B, V, _) = verts.device, verts.shape
+    (cover,), Bm, h, w = _mask_maps("silhouette_loss", cover)
+    allow_d2 = allow_d2.contiguous()
+    if Bm != B or tuple(allow_d2.shape) != (B, h, w) or allow_d2.dtype != torch.int32 or allow_d2.device != dev or cover.device != dev:
+        raise ValueError(f"silhouette_loss: allow_d2 int32 and cover float32, both ({B}, h, w) on {dev}; got {tuple(allow_d2.shape)} "
+                         f"{allow_d2.dtype} and {tuple(cover.shape)}")
+    K = K.detach().to(dev).float().reshape(B, 6).contiguous()
+    nv = _counts(n_verts, B, dev, "silhouette_loss: n_verts")
+    if weight is not None:
+        weight = torch.as_tensor(weight).detach().to(dev, torch.float32).contiguous()
+        if weight.shape not in ((V,), (B, V)):
+            raise ValueError(f"silhouette_loss: weight {tuple(weight.shape)}: ({V},) or ({B}, {V})")
+    stride = 0 if weight is None or weight.dim() == 1 else V
+    return _SilhouetteLoss.apply(verts, K, allow_d2, cover, nv, weight, stride, float(near))

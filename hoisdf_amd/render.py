@@ -28,6 +28,24 @@ def camera_rows(cam_intr: torch.Tensor) -> torch.Tensor:
     return (K[:, :2, :] if K.dim() == 3 else K).reshape(K.shape[0], 6).contiguous()
 
 
+def mask_camera_rows(cam_intr: torch.Tensor, cfg) -> torch.Tensor:
+    """meta["cam_intr"] -> K (B, 6) for the MASK grid of cfg.output_hm_shape, as ops.silhouette_loss takes it: a point that
+    projects onto the sample point of the raster pixel a mask pixel reads lands on that mask pixel.  The masks are the NEAREST fold of
+    a cfg.input_img_shape raster: mask pixel i reads raster pixel floor((i + .5) s) = s i + floor(s / 2), s = W / hm_w a whole
+    number, and that raster pixel is sampled at its index (cfg.raster_half_pixel: + 0.5).  So i = (u - floor(s / 2) - 0.5 half) / s:
+    the first row of K is divided by s after the offset left its third entry, the second row likewise with H / hm_h."""
+    K = camera_rows(cam_intr).clone()
+    hm_h, hm_w = _hm_shape(cfg)
+    H, W = int(cfg.input_img_shape[0]), int(cfg.input_img_shape[1])
+    if W % hm_w or H % hm_h:
+        raise ValueError(f"mask_camera_rows: the raster {W} x {H} must be a whole multiple of the mask grid {hm_w} x {hm_h}")
+    half = 0.5 if bool(cfg.raster_half_pixel) else 0.0
+    for row, s in ((0, W // hm_w), (1, H // hm_h)):
+        K[:, 3 * row + 2] -= s // 2 + half
+        K[:, 3 * row:3 * row + 3] /= s
+    return K
+
+
 def _hm_shape(cfg) -> Tuple[int, int]:
     return int(cfg.output_hm_shape[-2]), int(cfg.output_hm_shape[-1])
 

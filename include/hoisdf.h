@@ -1358,6 +1358,79 @@ int hoisdf_raster_overlay(const int32_t* id, const uint8_t* image_in, uint8_t* i
 int hoisdf_eval_silhouette(const float* pred_hand, const float* pred_obj, const float* gt_hand, const float* gt_obj, int B, int n,
                            int32_t* counts, void* stream);
 
+/* ---- silhouette loss: a mask's distance transform, and a projected point set held to a pair of mask maps, with gradients -----------
+ * reference: none - the reference supervises masks only at its CNN decoder.  Mesh regressors (HMR's descendants, SMPLify-X) hold a
+ * predicted mesh to a silhouette through the DISTANCE TRANSFORM of the target mask instead of a differentiable rasteriser: projected
+ * vertices are pulled into the silhouette, the silhouette's pixels are pulled under a projected vertex.  csrc/silhouette_loss.hip;
+ * hoisdf_amd/silhouette_loss_oracle.py restates the rules below in numpy.  Integers and fp64, no float atomics, every sum in one
+ * order: two calls give the same bits; a batch equals its samples run one by one, bit for bit.
+ * Every entry checks its arguments before any launch (HOISDF_ERR_INVALID, the argument named in hoisdf_last_error), returns 0 with
+ *   nothing launched for B = 0 (0 <= B <= 65535), and only enqueues on `stream`.  w, h in 1 .. HOISDF_EDT_MAX_SIZE.
+ *
+ * hoisdf_mask_edt (2 launches): the exact squared Euclidean distance transform.  mask, mask_or float [B][h][w], a value > 0.5 is set;
+ *   mask_or may be NULL, otherwise the set is the union of the two ("hand or object").  Checked: mask or d2_out null, w, h, B.
+ *     d2_out      int32 [B][h][w]: the squared distance in pixels^2 to the nearest set pixel of the sample, 0 at a set pixel,
+ *                 HOISDF_EDT_NONE (= 2^30 = (2^15)^2) everywhere in a sample without a set pixel
+ *     nearest_out int32, same shape, may be NULL: the index y' w + x' of a nearest set pixel, the LOWEST index on an exact tie; -1
+ *                 in a sample without a set pixel
+ *   Pass 1, one thread per column: g[y][x] = min |y - y'| over the set pixels of column x (the upper row on a tie), 2^15 for a
+ *   column without one.  Pass 2, a workgroup per row with the row's g^2 in LDS: d2 = min over x' of min(g[y][x']^2 + (x - x')^2,
+ *   HOISDF_EDT_NONE), every lane reading the same x'; ties by (y', x').  Integers only: no order dependence.  d2_out holds pass 1's
+ *   rows in between: no workspace.
+ *
+ * hoisdf_silhouette_loss_fwd (3 launches) / _bwd (1 launch): ONE point set against ONE pair of maps (a caller with a hand and an
+ *   object calls the pair twice).
+ *   verts [B][V][3] camera frame, metres, z forward; n_verts [B] DEVICE int32 or NULL = V, clamped to 0 .. V: rows from n_verts[b]
+ *   on are padding.  K [B][6] as hoisdf_raster_meshes takes it, but FOR THE MASK GRID: mask pixel (px, py) sits at (px, py).
+ *   allow_d2 int32 [B][h][w]: a d2_out of hoisdf_mask_edt - where the points may lie.  cover float [B][h][w], set where > 0.5: the
+ *   pixels the points must cover.  weight [V] floats per sample, may be NULL = all ones, weight_stride in elements 0 (one array
+ *   shared by the batch) or V.  near: finite, > 0.
+ *   Checked: verts, K, allow_d2, cover, an output or the workspace null; B; V < 1; w, h; near; a weight_stride that is neither 0 nor
+ *   V; a workspace below hoisdf_silhouette_loss_workspace_bytes(B, V, w, h) device bytes (-1 on an invalid shape).
+ *   Projection, per vertex: floats widened to fp64, no product fused into a sum:  u = ((K0 x + K1 y) + K2 z) / z,
+ *   v = ((K3 x + K4 y) + K5 z) / z.  A vertex is INVALID when a coordinate is not finite, when z < near, when its row is >=
+ *   n_verts[b], or when u or v is not finite: it takes no part in either term and gets zero gradient.
+ *   Inside term, per valid vertex: uc = clamp(u, 0, w-1), vc = clamp(v, 0, h-1); x0 = min(floor(uc), w-2), y0 = min(floor(vc), h-2)
+ *   (w = 1: x0 = 0 and the column weight fx is 0; h likewise); fx = uc - x0, fy = vc - y0; d = sqrt((double)allow_d2) at the four
+ *   corners;  val = ((1-fx)(1-fy) d00 + fx (1-fy) d10) + ((1-fx) fy d01 + fx fy d11);  out = sqrt((u-uc)^2 + (v-vc)^2): a vertex
+ *   that projects off the map is pulled back.  A corner with allow_d2 >= HOISDF_EDT_NONE (an empty allow mask) makes the vertex's
+ *   term 0 with zero gradient.
+ *     inside[b] = sum_v weight[v] (val + out) / sum_{v < n_verts[b]} weight[v]
+ *   The denominator does not depend on the geometry; one that is not positive gives 0.
+ *   Cover term, per set pixel p = (px, py) of cover: the nearest VALID vertex by dd = ((px-u)(px-u)) + ((py-v)(py-v)) in fp64, the
+ *   lowest vertex index on an exact tie.
+ *     cover_out[b] = sum_p sqrt(dd_p) / N_p,  N_p = the number of set pixels;  no set pixel, or no valid vertex, gives 0.
+ *   Sums in fp64: thread t of 256 takes elements (vertices, pixels) t, t + 256, ... in ascending order, the 256 partial sums meet
+ *   in the fixed tree s[t] += s[t + 128], s[t + 64], ... ; one rounding to fp32.
+ *   Forward kernels: the projection; one workgroup per sample and tile of 256 pixels with the sample's (u, v) pairs passing
+ *   through LDS, all lanes reading the same vertex, a wave without a set pixel skipping the scan; the per-sample reduction.
+ *   workspace: 256-byte aligned pieces in this order, each rounded up to 256 bytes:  u double [B][V];  v double [B][V];  cell int32
+ *   [B][V] = y0 w + x0, -1 for an invalid vertex;  nearest int32 [B][h w] = the nearest vertex of a set pixel, -1 for an unset
+ *   pixel (or without a valid vertex);  den double [B][2] = the weight denominator, N_p.  hoisdf_silhouette_loss_bwd reads it, so
+ *   between the two calls the workspace and every input stay as they were.
+ *   Backward: upstream gradients g_inside, g_cover [B] (either may be NULL = zero) -> d_verts [B][V][3]; every row is written, a
+ *   padding or invalid row gets 0.  Chain rule: du/dx = K0 / z, du/dy = K1 / z, du/dz = (K2 - u) / z, and likewise for v.
+ *   Inside term: the bilinear derivative in fx, fy, zero along an axis that was clamped, plus the unit vector of (u-uc, v-vc) where
+ *   out > 0, times weight / denominator times g_inside.  Cover term: vertex n receives (g_cover / N_p) ((u_n, v_n) - p) / sqrt(dd_p)
+ *   from every set pixel whose nearest vertex it is; a pixel with dd_p = 0 contributes nothing.
+ *   Order: no atomics; each vertex is owned by one lane, which adds in fp64, in (u, v), its own inside term first, then the pixels
+ *   in ASCENDING pixel index (staged through LDS in tiles of HOISDF_SIL_LOSS_TILE records), applies the chain rule and rounds to
+ *   fp32 once. */
+#define HOISDF_EDT_MAX_SIZE 512
+#define HOISDF_EDT_NONE 1073741824
+#define HOISDF_SIL_LOSS_TILE 64
+int hoisdf_mask_edt(const float* mask, const float* mask_or, int B, int w, int h, int32_t* d2_out, int32_t* nearest_out, void* stream);
+long hoisdf_silhouette_loss_workspace_bytes(int B, int V, int w, int h);
+int hoisdf_silhouette_loss_fwd(const float* verts, const int32_t* n_verts, int V, const float* K, int B,
+                               const int32_t* allow_d2, const float* cover, int w, int h, float near,
+                               const float* weight, long weight_stride,
+                               float* inside, float* cover_out, void* workspace, long workspace_bytes, void* stream);
+int hoisdf_silhouette_loss_bwd(const float* verts, const int32_t* n_verts, int V, const float* K, int B,
+                               const int32_t* allow_d2, const float* cover, int w, int h, float near,
+                               const float* weight, long weight_stride,
+                               const float* g_inside, const float* g_cover,
+                               float* d_verts, const void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

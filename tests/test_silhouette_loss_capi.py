@@ -1,0 +1,159 @@
+"""CPU: the silhouette-loss entries of the C ABI (include/hoisdf.h hoisdf_mask_edt, hoisdf_silhouette_loss_fwd / _bwd,
+csrc/silhouette_loss.hip) refuse malformed calls with HOISDF_ERR_INVALID and a message that names the argument before anything is
+launched (no GPU here: a launch would fail loudly), return 0 for an empty batch, their workspace query is arithmetic, and the
+Python surface is opt-in."""
+import ctypes as C
+import inspect
+import os
+
+import pytest
+
+from hoisdf_amd import _lib
+
+INVALID = -1
+FAKE = C.c_void_p(0x100000)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib.lib()
+
+
+def test_the_entries_and_their_constants_are_declared_and_exported(lib):
+    edt, fwd, bwd = (_lib.SIGNATURES[n] for n in ("hoisdf_mask_edt", "hoisdf_silhouette_loss_fwd", "hoisdf_silhouette_loss_bwd"))
+    assert len(edt) == 8 and edt[2:5] == [C.c_int] * 3
+    assert len(fwd) == 17 and len(bwd) == 18 and fwd[:12] == bwd[:12] and fwd[9] is C.c_float and fwd[11] is C.c_long and fwd[-1] is C.c_void_p
+    assert _lib._OTHER["hoisdf_silhouette_loss_workspace_bytes"] == ([C.c_int] * 4, C.c_long)
+    assert _lib.CONSTANTS["EDT_MAX_SIZE"] == 512 and _lib.CONSTANTS["EDT_NONE"] == 1 << 30 and _lib.CONSTANTS["SIL_LOSS_TILE"] == 64
+    for name in ("hoisdf_mask_edt", "hoisdf_silhouette_loss_fwd", "hoisdf_silhouette_loss_bwd", "hoisdf_silhouette_loss_workspace_bytes"):
+        assert hasattr(lib, name), name
+
+
+def test_the_workspace_query_is_arithmetic(lib):
+    q = lib.hoisdf_silhouette_loss_workspace_bytes
+    B, V, w, h = 4, 778, 128, 96
+    need = q(B, V, w, h)
+    up = lambda n: (n + 255) // 256 * 256
+    # u and v as doubles, the cell per vertex, the nearest vertex per pixel, two doubles per sample: each piece a multiple of 256 bytes
+    assert need == 2 * up(B * V * 8) + up(B * V * 4) + up(B * w * h * 4) + up(B * 16) and need % 256 == 0
+    assert q(2 * B, V, w, h) > need and q(B, V, w, h) == need and q(B, V, h, w) == need
+    assert q(0, 1, 1, 1) == 0
+    assert q(B, 0, w, h) == INVALID and b"V=0" in lib.hoisdf_last_error()
+    assert q(B, V, 513, h) == INVALID and b"w=513" in lib.hoisdf_last_error()
+    assert q(B, V, w, 0) == INVALID and b"h=0" in lib.hoisdf_last_error()
+    assert q(-1, V, w, h) == INVALID and q(65536, V, w, h) == INVALID and b"B=65536" in lib.hoisdf_last_error()
+
+
+def test_mask_edt_checks_its_arguments_before_any_launch(lib):
+    def call(mask=FAKE, mask_or=None, B=2, w=48, h=40, d2=FAKE, nearest=None):
+        return lib.hoisdf_mask_edt(mask, mask_or, B, w, h, d2, nearest, None)
+
+    for kw, what in ((dict(mask=None), b"mask"), (dict(d2=None), b"d2_out")):
+        assert call(**kw) == INVALID and b"null" in lib.hoisdf_last_error() and what in lib.hoisdf_last_error(), kw
+    for kw, what in ((dict(w=0), b"w=0"), (dict(w=513), b"w=513"), (dict(h=0), b"h=0"), (dict(h=513), b"h=513"), (dict(B=-1), b"B=-1"),
+                     (dict(B=65536), b"B=65536")):
+        assert call(**kw) == INVALID and what in lib.hoisdf_last_error() and b"mask_edt" in lib.hoisdf_last_error(), kw
+    assert call(B=0, mask=None, d2=None) == 0
+
+
+@pytest.mark.parametrize("entry", ["fwd", "bwd"])
+def test_both_loss_entries_check_their_arguments_before_any_launch(lib, entry):
+    need = lib.hoisdf_silhouette_loss_workspace_bytes(4, 778, 128, 128)
+    outs = ("inside", "cover_out") if entry == "fwd" else ("d_verts",)
+
+    def call(verts=FAKE, nv=None, V=778, K=FAKE, B=4, d2=FAKE, cover=FAKE, w=128, h=128, near=0.01, wt=None, stride=0, ws=FAKE, nws=need, **out):
+        head = (verts, nv, V, K, B, d2, cover, w, h, near, wt, stride)
+        ptrs = [out.get(k, FAKE) for k in outs]
+        if entry == "fwd":
+            return lib.hoisdf_silhouette_loss_fwd(*head, *ptrs, ws, nws, None)
+        return lib.hoisdf_silhouette_loss_bwd(*head, None, None, *ptrs, ws, nws, None)
+
+    nulls = ((dict(verts=None), b"verts"), (dict(K=None), b"K"), (dict(d2=None), b"allow_d2"), (dict(cover=None), b"cover"), (dict(ws=None), b"workspace"))
+    for kw, what in nulls + tuple((dict([(k, None)]), k.encode()) for k in outs):
+        assert call(**kw) == INVALID and b"null" in lib.hoisdf_last_error() and what in lib.hoisdf_last_error(), (kw, lib.hoisdf_last_error())
+    inf, nan = float("inf"), float("nan")
+    for kw, what in ((dict(B=-1), b"B=-1"), (dict(B=65536), b"B=65536"), (dict(V=0), b"V=0"), (dict(w=0), b"w=0"), (dict(w=513), b"w=513"),
+                     (dict(h=0), b"h=0"), (dict(h=513), b"h=513"), (dict(near=0.0), b"near=0"), (dict(near=-0.01), b"near=-0.01"),
+                     (dict(near=inf), b"near=inf"), (dict(near=nan), b"near="), (dict(wt=FAKE, stride=777), b"weight_stride=777"),
+                     (dict(wt=FAKE, stride=-1), b"weight_stride=-1"), (dict(nws=need - 1), b"workspace"), (dict(nws=0), b"workspace")):
+        assert call(**kw) == INVALID and what in lib.hoisdf_last_error(), (kw, lib.hoisdf_last_error())
+        assert f"silhouette_loss_{entry}".encode() in lib.hoisdf_last_error()
+    # B = 0: nothing to do, whatever the pointers
+    assert call(B=0, verts=None, K=None, d2=None, cover=None, ws=None, nws=0, **{k: None for k in outs}) == 0
+    assert call(B=0, wt=FAKE, stride=778, ws=None, nws=0) == 0
+
+
+def test_python_surface_is_opt_in(monkeypatch):
+    import torch
+    from hoisdf_amd import engine, ops, render, silhouette_loss_oracle
+    from hoisdf_amd.config import Config
+    from hoisdf_amd.model import get_model
+    monkeypatch.delenv("HOISDF_SILHOUETTE_LOSS", raising=False)
+    c = Config()
+    assert c.silhouette_loss is False and c.silhouette_in_weight > 0 and c.silhouette_cover_weight > 0
+    assert engine.LOSS_WEIGHTS["silhouette_in"] == "silhouette_in_weight" and engine.LOSS_WEIGHTS["silhouette_cover"] == "silhouette_cover_weight"
+    assert all(hasattr(c, a) for a in engine.LOSS_WEIGHTS.values())
+    c.resnet_type = 18
+    m = get_model("train", cfg=c, with_encoder=False)
+    assert not m.silhouette_loss_enabled() and m._interaction is None
+    monkeypatch.setenv("HOISDF_SILHOUETTE_LOSS", "1")
+    assert m.silhouette_loss_enabled() and not m.interaction_loss_enabled()
+    monkeypatch.delenv("HOISDF_SILHOUETTE_LOSS")
+    c.silhouette_loss = True
+    assert m.silhouette_loss_enabled()
+    ik = Config()
+    ik.resnet_type = 18
+    ik.apply_setting("ho3d_render")
+    ik.silhouette_loss = True
+    with pytest.raises(ValueError, match="silhouette_loss"):
+        get_model("train", cfg=ik, with_encoder=False)
+    sig = inspect.signature(ops.silhouette_loss).parameters
+    assert list(sig) == ["verts", "K", "allow_d2", "cover", "n_verts", "weight", "near"] and sig["n_verts"].default is None and sig["weight"].default is None
+    assert list(inspect.signature(ops.mask_edt).parameters) == ["mask", "mask_or", "want_nearest"]
+    with pytest.raises(RuntimeError, match="no CPU fallback"):           # like every op
+        ops.mask_edt(torch.zeros(1, 4, 4))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.silhouette_loss(torch.zeros(1, 5, 3), torch.zeros(1, 6), torch.zeros(1, 4, 4, dtype=torch.int32), torch.zeros(1, 4, 4))
+    assert silhouette_loss_oracle.EDT_NONE == _lib.CONSTANTS["EDT_NONE"]
+    # nothing on the product path imports the restatement
+    import hoisdf_amd
+    root = os.path.dirname(hoisdf_amd.__file__)
+    for name in ("ops.py", "model.py", "engine.py", "render.py", "sdf_data.py", "metrics.py"):
+        assert "silhouette_loss_oracle" not in open(os.path.join(root, name)).read(), name
+    assert callable(render.mask_camera_rows)
+
+
+def test_the_mask_grid_camera():
+    """mask pixel i reads raster pixel floor((i + .5) s), sampled at its index (+ 0.5 with raster_half_pixel): a point that
+    projects there lands on mask pixel i"""
+    import torch
+    from hoisdf_amd.config import Config
+    from hoisdf_amd.render import camera_rows, mask_camera_rows
+    c = Config()
+    c.input_img_shape, c.output_hm_shape = (256, 512), (64, 64, 128)           # s = 4 both ways
+    cam = torch.tensor([[[500.0, 3.0, 130.0], [0.0, 480.0, 120.0], [0.0, 0.0, 1.0]]])
+    for half in (False, True):
+        c.raster_half_pixel = half
+        K, Km = camera_rows(cam)[0].double(), mask_camera_rows(cam, c)[0].double()
+        for i, j in ((0, 0), (7, 40), (127, 63)):
+            u, v = (i * 4 + 2) + 0.5 * half, (j * 4 + 2) + 0.5 * half        # the raster sample point mask pixel (i, j) reads
+            y = (v - K[5]) / K[4]                                             # a point at z = 1 that projects to (u, v)
+            x = (u - K[2] - K[1] * y) / K[0]
+            assert abs(float(Km[0] * x + Km[1] * y + Km[2]) - i) < 1e-4 and abs(float(Km[3] * x + Km[4] * y + Km[5]) - j) < 1e-4
+    c.output_hm_shape = (64, 64, 100)
+    with pytest.raises(ValueError, match="multiple"):
+        mask_camera_rows(cam, c)
+
+
+def test_the_header_states_the_rules_the_tests_and_the_oracle_rely_on():
+    text = " ".join(open(_lib.HEADER_PATH).read().split())
+    for phrase in ("the LOWEST index on an exact tie", "HOISDF_EDT_NONE (= 2^30 = (2^15)^2)", "u = ((K0 x + K1 y) + K2 z) / z",
+                   "x0 = min(floor(uc), w-2)", "val = ((1-fx)(1-fy) d00 + fx (1-fy) d10) + ((1-fx) fy d01 + fx fy d11)",
+                   "inside[b] = sum_v weight[v] (val + out) / sum_{v < n_verts[b]} weight[v]", "cover_out[b] = sum_p sqrt(dd_p) / N_p",
+                   "one that is not positive gives 0", "s[t] += s[t + 128], s[t + 64]", "[B][V] = y0 w + x0, -1 for an invalid vertex",
+                   "every row is written", "ASCENDING pixel index", "no atomics", "tiles of HOISDF_SIL_LOSS_TILE records",
+                   "two calls give the same bits", "a batch equals its samples run one by one", "a pixel with dd_p = 0 contributes nothing"):
+        assert phrase in text, phrase
