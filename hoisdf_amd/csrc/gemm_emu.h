@@ -203,7 +203,8 @@ __device__ __forceinline__ void emu_epilogue(const EmuArgs& g, f32x16 (&acc)[4][
   }
   if (g.head_out) {
     // head magnitudes (common.h): each 64-column group of the wave's 128-row sub-tile -> the word(s) of the sample(s) its rows belong to
-    // (one sample when head_L % 128 == 0; otherwise every sample the 128 rows touch gets the whole sub-tile's maximum: an upper bound)
+    // (exact only when a sub-tile is one sample's: the host sets head_out when head_L % 128 == 0 and M % 128 == 0 and measures the stored
+    // matrix otherwise - gemm_emu.hip heads_fold_exact(); a sub-tile of several samples would give each of them the maximum of all)
     const int row0 = m0 + wm * 128;
     if (row0 < g.M) {
       const int b0 = row0 / g.head_L, b1 = (min(row0 + 127, g.M - 1)) / g.head_L;

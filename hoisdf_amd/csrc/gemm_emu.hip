@@ -125,6 +125,10 @@ int emu_headmag_launch(const float* x, long ld, long M, int groups, int L, uint3
   return check_launch("emu_headmag");
 }
 bool emu_form_h2() { return form_h2(); }
+// may the GEMM epilogue fold the head magnitudes of its output?  Its unit is the wave's 128-row sub-tile: exact only when every
+// sub-tile lies inside one sample and holds no rows past M (those carry the bias).  Otherwise the words are measured on the stored
+// matrix (emu_headmag_launch): a sample's scale must not depend on its batch neighbours.
+static bool heads_fold_exact(long M, int head_L) { return head_L % 128 == 0 && M % 128 == 0; }
 
 namespace {
 int launch_emu(EmuArgs g, hipStream_t st) {
@@ -221,11 +225,18 @@ int hoisdf::linear_fwd_emu_mag(const float* x, int ldx, const void* w_image, con
   g.act = act; g.drop_p = drop_p; g.inv_keep = 1.f / (1.f - drop_p); g.thresh = drop_threshold(drop_p); g.seed = seed;
   g.bits_out = relu_bits; g.ldbits_out = (N + 31) / 32;
   g.a_amax = x_mag; g.amax_out = y_mag;
+  bool measure_heads = false;
   if (y_heads) {
     HOISDF_REQUIRE(head_L > 0 && N % 64 == 0, HOISDF_ERR_INVALID, "linear_fwd_emu: head magnitudes need N %% 64 == 0 and the rows per sample");
-    g.head_out = y_heads; g.head_L = head_L; g.head_nb = cdiv(M, head_L);
+    if (heads_fold_exact(M, head_L)) { g.head_out = y_heads; g.head_L = head_L; g.head_nb = cdiv(M, head_L); }
+    else {
+      HOISDF_REQUIRE(al16(y) && ldy % 4 == 0, HOISDF_ERR_INVALID, "linear_fwd_emu: head magnitudes of samples that are no multiple of 128 rows need y 16-byte aligned, ldy %% 4 == 0");
+      measure_heads = true;
+    }
   }
-  return launch_emu(g, as_stream(stream));
+  if (int rc = launch_emu(g, as_stream(stream))) return rc;
+  // samples that share 128-row sub-tiles: the words of the stored y, one more read of it (what hoisdf_head_mag_measure gives)
+  return measure_heads ? emu_headmag_launch(y, ldy, M, N / 64, head_L, y_heads, as_stream(stream)) : HOISDF_OK;
 }
 
 // hoisdf_linear_fwd_emu whose output goes into attention planes (common.h QkvPlanes; internal: the coarse layer entries use it)
@@ -282,11 +293,17 @@ int hoisdf::linear_bwd_input_emu_mag(const float* dy, int lddy, const uint32_t* 
   g.inv_keep = 1.f;
   g.beta = accumulate ? 1 : 0;
   g.a_amax = dy_mag; g.amax_out = dx_mag;
+  bool measure_heads = false;
   if (dx_heads) {
     HOISDF_REQUIRE(head_L > 0 && K % 64 == 0 && !accumulate, HOISDF_ERR_INVALID, "linear_bwd_input_emu: head magnitudes need K %% 64 == 0, the rows per sample, no accumulation");
-    g.head_out = dx_heads; g.head_L = head_L; g.head_nb = cdiv(M, head_L);
+    if (heads_fold_exact(M, head_L)) { g.head_out = dx_heads; g.head_L = head_L; g.head_nb = cdiv(M, head_L); }
+    else {
+      HOISDF_REQUIRE(al16(dx) && lddx % 4 == 0, HOISDF_ERR_INVALID, "linear_bwd_input_emu: head magnitudes of samples that are no multiple of 128 rows need dx 16-byte aligned, lddx %% 4 == 0");
+      measure_heads = true;
+    }
   }
-  return launch_emu(g, as_stream(stream));
+  if (int rc = launch_emu(g, as_stream(stream))) return rc;
+  return measure_heads ? emu_headmag_launch(dx, lddx, M, K / 64, head_L, dx_heads, as_stream(stream)) : HOISDF_OK;
 }
 
 extern "C" long hoisdf_linear_bwd_weight_emu_workspace(long M, int N, int K) {

@@ -160,6 +160,8 @@ int forward(const float* x, const hoisdf_encoder_layer_weights* w, const hoisdf_
       }
     }
   } else if (g.full) {
+    // (head magnitudes: folded by the GEMM epilogue when S / nq are multiples of its 128-row sub-tile, otherwise measured on the stored
+    // matrix behind it - linear_fwd_emu_mag decides; either way each sample's own maximum, as the op chain's hoisdf_head_mag_measure)
     lin_fwd(c, x, E, w->w_in, E, w->img_in, w->b_in, s.qkv, 3 * E, g.Ms, 3 * E, E, 0, 0.f, 0, nullptr, 0, xm, nullptr,
             g.att_h2 ? head_q(g, smag) : nullptr, g.S);
     q = s.qkv; k = s.qkv + E; v = s.qkv + 2 * E; ldq = ldkv = 3 * E;

@@ -165,8 +165,11 @@ int hoisdf_linear_emu_supported(const float* a, long lda, int contraction);
  *       the LayerNorm, gather, positional-encoding, SDF-head and attention entries of the composite calls.  Without words (x_mag =
  *       NULL, and in the plain entries) the library measures the operand itself: one more read of it (hoisdf_mag_measure does the
  *       same once for several consumers).  HEAD MAGNITUDES of an attention operand matrix (rows = B samples x L tokens, groups of 64
- *       columns = heads): hoisdf_head_mag_words(M, groups, L) words, word[group * B + sample]; zero-filled, then folded by
- *       hoisdf_linear_fwd_emu_heads / the composite entries, or made by hoisdf_head_mag_measure.
+ *       columns = heads): hoisdf_head_mag_words(M, groups, L) words, word[group * B + sample] = the IEEE bits of the maximum magnitude
+ *       of THAT sample's rows in the group, exactly, for any L; zero-filled, then left by hoisdf_linear_fwd_emu_heads /
+ *       hoisdf_linear_bwd_input_emu_heads / the composite entries, or made by hoisdf_head_mag_measure.  (The GEMM epilogue folds them
+ *       where each of its 128-row sub-tiles lies inside one sample - L and M multiples of 128; otherwise those entries read the stored
+ *       matrix once more, as hoisdf_head_mag_measure does: one more launch on the same stream, the same words.)
  *       A word SMALLER than the true maximum (a stale array) cannot make Inf / NaN: the splitting kernels run with f16 saturation
  *       on (MODE.FP16_OVFL) - up to 4x too small is harmless (head room of the [2^13, 2^14) target), beyond that the row's largest
  *       elements clip at 65504 / scale.
@@ -178,8 +181,9 @@ int hoisdf_mag_measure(const float* x, long ldx, long M, int K, uint32_t* words,
 long hoisdf_head_mag_words(long M, int groups, int L);
 /* the head magnitudes of x[M][>= groups * 64] (samples of L consecutive rows): clears `words`, then one read of x */
 int hoisdf_head_mag_measure(const float* x, long ldx, long M, int groups, int L, uint32_t* words, void* stream);
-/* hoisdf_linear_fwd_emu_mag that also folds the head magnitudes of y (N % 64 == 0; zero-filled `y_heads`, samples of L rows) - what an
- * attention in-projection leaves for hoisdf_attention_fwd_emu_mag; y_mag may be NULL */
+/* hoisdf_linear_fwd_emu_mag that also leaves the head magnitudes of the stored y (N % 64 == 0; zero-filled `y_heads`, samples of L rows,
+ * any L: each sample's own maximum; L or M not a multiple of 128: y 16-byte aligned, ldy % 4 == 0) - what an attention in-projection
+ * leaves for hoisdf_attention_fwd_emu_mag; y_mag may be NULL */
 int hoisdf_linear_fwd_emu_heads(const float* x, int ldx, const void* w_image, const float* bias, float* y, int ldy, long M, int N,
                                 int K, const uint32_t* x_mag, uint32_t* y_mag, uint32_t* y_heads, int L, void* stream);
 /* the same for a grad-input (no sign bitmap, no accumulation): what an out-projection's backward leaves for the dO operand of
