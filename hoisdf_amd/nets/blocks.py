@@ -266,7 +266,7 @@ class TransformerDecoder(nn.Module):
         B = memory.shape[0]
         n = self.norm
         l0 = self.layers[0]
-        if not self.normalize_before and ops.decoder_layer_ok(l0.p if l0.training else 0.0, memory, query_embed, l0.linear1.weight):
+        if not self.normalize_before and ops.decoder_layer_ok(l0.p if l0.training else 0.0, memory, query_embed, *self.parameters()):
             # one C-ABI call per layer and direction (csrc/layers.hip hoisdf_decoder_layer_fwd / _bwd)
             x = torch.zeros(B, query_embed.shape[0], query_embed.shape[1], device=memory.device)
             outs = []

@@ -1313,7 +1313,7 @@ class _EncoderLayer(torch.autograd.Function):
     x (B,S,E); n_query < S: only the first n_query rows are produced (keys / values still come from all S rows)."""
 
     @staticmethod
-    def forward(ctx, x, n_query, p, H, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3, eps, n_inter=None):
+    def forward(ctx, x, n_query, p, H, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3, eps, n_inter=None, f16=False):
         x = x.contiguous()
         _chk(x, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3)
         B, S, E = x.shape
@@ -1339,8 +1339,9 @@ class _EncoderLayer(torch.autograd.Function):
             kv3 = kvbuf.view(B, S, 2 * E)
             k, v = kv3[:, :, :E], kv3[:, :, E:]
         heads = None
-        if _use_f16(p, x, w_in, w_out, w1, w2):
-            # gradient-free eval with cfg.attention_f16_eval: the f16-operand kernel (no LSE: nothing is saved for a backward)
+        if f16:
+            # gradient-free eval with cfg.attention_f16_eval: the f16-operand kernel (no LSE: nothing is saved for a backward).
+            # (encoder_layer() decides: grad mode is off inside a Function's forward, where _use_f16 would always say yes)
             o, lse = _attn_fwd_f16(q, k, v, H, S), None
         else:
             if emulated and _attn_h2(B * nq) and E == 64 * H:
@@ -1382,6 +1383,8 @@ class _EncoderLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_x2, g_y):
         (x, qs, ks, o, lse, a, x1, h, bits, f, x2, st, w_in, w_out, w1, w2, g1, g2, g3) = ctx.saved_tensors
+        if lse is None:
+            raise RuntimeError("encoder_layer: backward of the f16 evaluation forward, which keeps no log-sum-exp")
         B, S, E, nq, full, p, H, (s_attn, s_ln1, s_ffn, s_ln2), emulated, ni = ctx.meta
         dev = x.device
         M, F = B * nq, w1.shape[0]
@@ -1442,7 +1445,7 @@ class _EncoderLayer(torch.autograd.Function):
             _lin_bwd_weight(dkv.view(B * S, 2 * E), None, 0.0, x.view(B * S, E), dw_in[E:], db_in[E:])
             dx = dxf.view(B, S, E)
             dx[:, :nq] += dxq.view(B, nq, E)
-        return (dx, None, None, None, dw_in, db_in, dw_out, db_out, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2, dg3, dbe3, None, None)
+        return (dx, None, None, None, dw_in, db_in, dw_out, db_out, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2, dg3, dbe3, None, None, None)
 
 
 class _EncoderLayerC(torch.autograd.Function):
@@ -1543,9 +1546,11 @@ def _coarse_layer_ok(p, x, *weights) -> bool:
 def encoder_layer(x, n_query, p, H, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3, eps=1e-5,
                   n_inter=None):
     """-> (x2 (B, n_query|S, E) = the layer output, y = inter_norm(x2) (B, n_inter|n_query|S, E): rows < n_inter only)"""
-    fn = _EncoderLayerC if _coarse_layer_ok(float(p), x, w_in, w_out, w1, w2) else _EncoderLayer
-    return fn.apply(x, n_query, float(p), int(H), w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3,
-                               be3, float(eps), n_inter)
+    params = (w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3)
+    args = (x, n_query, float(p), int(H), *params, float(eps), n_inter)
+    if _coarse_layer_ok(float(p), x, *params):
+        return _EncoderLayerC.apply(*args)
+    return _EncoderLayer.apply(*args, _use_f16(float(p), x, *params))        # (every tensor of the call: any of them may bring a backward)
 
 
 class _DecoderLayerC(torch.autograd.Function):
@@ -2167,6 +2172,8 @@ class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, training, momentum, eps, relu):
         _chk(x, weight, bias, residual)
+        # (decided here, on the caller's tensors: a layout copy made below is made in the Function's no-grad mode and requires nothing)
+        need_grad = training and any(ctx.needs_input_grad[:4])     # x, weight, bias, residual
         n, c, h, w = x.shape
         M = n * h * w
         x, ldx = _rows_cl(x)
@@ -2175,8 +2182,6 @@ class _BnAct(torch.autograd.Function):
             assert residual.shape == x.shape, (residual.shape, x.shape)
             residual, ldr = _rows_cl(residual)
         y = torch.empty((n, h, w, c), device=x.device, dtype=torch.float32).permute(0, 3, 1, 2)      # channels_last, dense rows
-        need_grad = training and (x.requires_grad or (weight is not None and weight.requires_grad) or
-                                  (residual is not None and residual.requires_grad))
         if training:
             nws = _bn_workspace_floats(M, c)
             ws = torch.empty(nws, device=x.device, dtype=torch.float32)
@@ -2198,6 +2203,8 @@ class _BnAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, mean, invstd, bits = ctx.saved_tensors
         M, c, ldx, has_res, relu, has_w, has_b = ctx.meta
+        if relu and bits is None:                  # (a null sign map tells hoisdf_bn_bwd that no ReLU was applied)
+            raise RuntimeError("bn_act: backward of a ReLU forward that kept no sign map")
         dy, lddy = _rows_cl(dy)
         n, _, h, w = x.shape
         dx = torch.empty((n, h, w, c), device=x.device, dtype=torch.float32).permute(0, 3, 1, 2)
@@ -2213,7 +2220,15 @@ class _BnAct(torch.autograd.Function):
 def bn_act(x, weight, bias, running_mean, running_var, training: bool, momentum, eps: float, relu: bool, residual=None):
     """(f4) relu?(batch_norm(x) (+ residual)) of a channels_last map in two HBM passes per direction (csrc/bnact.hip);
     training: batch statistics, running statistics updated in place as torch.nn.functional.batch_norm does;
-    otherwise the running statistics normalise (no gradient path: evaluation)."""
+    otherwise the running statistics normalise (no gradient path: evaluation, refused for an input that requires a gradient).
+    momentum=None (torch's cumulative average over num_batches_tracked) is refused when running statistics are to be updated."""
+    if training and momentum is None and (running_mean is not None or running_var is not None):
+        raise ValueError("bn_act: momentum=None (cumulative moving average) is not implemented for running statistics; "
+                         "pass a momentum, or no running statistics")
+    # (here, not in the Function: its forward runs with grad mode off and cannot tell a no_grad evaluation from a call a backward follows)
+    if not training and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, residual)):
+        raise RuntimeError("bn_act: training=False normalises with the running statistics and keeps nothing for a backward; "
+                           "an input that requires a gradient needs training=True (or torch's batch_norm)")
     return _BnAct.apply(x, weight, bias, residual, running_mean, running_var, bool(training), momentum, float(eps), bool(relu))
 
 

@@ -925,11 +925,13 @@ int hoisdf_aux_image_losses_bwd(const float* dec, long sb, long sc, long sh, lon
  * torch.nn.functional.batch_norm(training) [+ add] + relu and its autograd backward.  The convolutions stay MIOpen's.
  * A channels_last (N, C, H, W) map is the row-major matrix [M = N H W][C] (row stride ld >= C, ld % 4 == 0; C % 8 == 0,
  * C <= 2048).  hoisdf_bn_stats: batch mean and 1 / sqrt(biased variance + eps) per channel (shifted f32 sums per block, f64
- * combination in block order by the last block: bit-reproducible), running statistics updated as torch does (unbiased
- * variance, momentum; NULL = not tracked).  hoisdf_bn_apply_fwd: y [M][C] dense = relu?((x - mean) gamma invstd + beta
+ * combination in slice order by a finishing kernel the same call queues: bit-reproducible), running statistics updated as
+ * torch does (unbiased variance, momentum - a number: torch's momentum=None cumulative average is not offered; NULL = not tracked).  hoisdf_bn_apply_fwd: y [M][C] dense = relu?((x - mean) gamma invstd + beta
  * (+ residual)); second_is_variance = 1: the fourth argument holds variances (evaluation mode: the running statistics);
  * sign_bits [M][C / 8] bytes (bit j of byte (row, c / 8) = y[row][c + j] > 0; NULL = not wanted).  hoisdf_bn_bwd: dx [M][C]
- * dense, d_residual (NULL = no residual) = dy masked by the sign bits (NULL = no ReLU), dgamma / dbeta [C] overwritten.
+ * dense, d_residual (NULL = no residual) = dy masked by the sign bits, dgamma / dbeta [C] overwritten (NULL = not wanted),
+ * gamma NULL = no affine.  A NULL sign_bits MEANS that the forward applied no ReLU: the gradient then passes unmasked, so the
+ * backward of a ReLU forward must hand in the map that forward wrote (there is no way to recompute it here).
  * workspace: hoisdf_bn_workspace_floats(M, C) floats. */
 long hoisdf_bn_workspace_floats(long M, int C);
 int hoisdf_bn_stats(const float* x, long ldx, long M, int C, float* mean, float* invstd, float* running_mean,
