@@ -377,11 +377,11 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def field_surface(self, feature_pyramid, meta_info, kind="hand", n=64, coarse_n=32, box=None, return_values=False, *,
-                      max_verts=None, max_faces=None, chunk_rows=None):
+                      max_verts=None, max_faces=None, chunk_rows=None, pad_cells=1):
         """The zero level set of the learned hand / object field as an indexed triangle mesh in camera metres (include/hoisdf.h
         "iso-surface"; no reference counterpart).  Coarse grid of ``coarse_n`` nodes per axis over the lattice cube [-1, 1]^3 of
         the scaled frame (``box`` (B, 2, 3): that region per sample instead) -> the field on its nodes -> hoisdf_iso_refine_grid
-        (pad 1: the box of the inside nodes, no host read) -> the field on the ``n`` fine nodes per axis -> hoisdf_iso_extract at
+        (``pad_cells`` = 1: the box of the inside nodes, no host read) -> the field on the ``n`` fine nodes per axis -> hoisdf_iso_extract at
         level 0 of sdf_raw (the unclamped tanh sdf_infer ranks on), vertices stored as x / scale + centre.
         Decoder dropout is off whatever the module's mode.  The queries go in chunks of at most FIELD_CHUNK_ROWS = 262144 rows with
         their sample index (``chunk_rows`` overrides it), of equal size up to a multiple of 256, so hoisdf_sdf_query_workspace stays
@@ -414,7 +414,7 @@ class Model(nn.Module):
         hi = torch.full((B, 3), 1.0, device=dev) if box is None else box[:, 1].to(dev).float()
         coarse_grid = torch.cat([lo, (hi - lo) / float(coarse_n - 1), torch.zeros(B, 2, device=dev)], 1)
         coarse = field(coarse_grid, coarse_n)
-        grid = ops.iso_refine_grid(coarse, coarse_grid, coarse_n, 0.0, 1, n)
+        grid = ops.iso_refine_grid(coarse, coarse_grid, coarse_n, 0.0, int(pad_cells), n)
         values = field(grid, n)
         res = ops.iso_surface(values, grid, n, 0.0, max_verts, max_faces, out_scale=1.0 / scale, out_shift=center)
         if return_values:
