@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._marshal import _chk
 from .config import cfg as _global_cfg
 from .nets.blocks import MLP, SDFDecoder, Transformer, VoteTransformer
 from .nets.encoder import BackboneNet, DecoderNet
@@ -752,7 +753,7 @@ class Model(nn.Module):
         infer_native_begin queued ahead of the encoder.  The default arithmetic only (cfg.attention_f16_eval is not offered)."""
         pyr = self._pyramid(pyr)
         root = meta_info["mano_root"]
-        ops._chk(root, self.hand_sigmoid_beta)          # GPU tensors only: there is no CPU form of this path
+        _chk(root, self.hand_sigmoid_beta)         # GPU tensors only: there is no CPU form of this path
         prepared = self._pose_prepared(root.shape[0], pyr.C, root.device)
         return ops.pose_infer(prepared, pyr, root, meta_info["obj_center_cam"], meta_info["cam_intr"], meta_info["bbox_hand"],
                               meta_info["bbox_obj"], counts, _StreamPlan(self, root.device).side, debug)
@@ -798,7 +799,7 @@ class Model(nn.Module):
     def encode_native(self, img, want_aux=True):
         """backbone_net + decoder_net in evaluation mode through ONE C-ABI call (hoisdf_encoder_infer: exact-f32 HIP convolutions,
         BatchNorm folded): ``img`` (B, 3, H, W) -> (PyramidNHWC, aux NHWC [B][H / 2][W / 2][3] or None).  Running statistics only."""
-        ops._chk(img)
+        _chk(img)
         prepared = self._encoder_prepared(img.shape[0], img.shape[2], img.shape[3], img.device)
         return ops.encoder_infer(prepared, img, want_aux)
 

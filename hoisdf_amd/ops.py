@@ -3,6 +3,12 @@
 PyTorch is plumbing here: it owns device memory, streams and the autograd tape.  All
 arithmetic of the hot path runs in libhoisdf_hip.so.  There is no CPU or eager fallback: a
 CPU tensor or a missing library raises.
+
+This module is the model's step: everything a training or evaluation step of Model.hot_path runs, and the process-wide state
+those calls read (dropout seeds, the zero arena, the emulation switches, the weight generation).  The stateless entries live by
+kernel family in ops_eval (evaluation metrics), ops_mesh (mesh SDF, interaction, iso-surface, rasteriser, silhouette) and
+ops_infer (whole-model / encoder inference, convolutions, IK) on the shared helpers of _marshal, and are re-exported here: callers
+keep saying ``ops.NAME``.  The import graph is _lib <- _marshal <- ops_eval / ops_mesh / ops_infer <- ops.
 """
 from __future__ import annotations
 
@@ -11,13 +17,22 @@ import math
 import os
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import (MLP_MAX_LAYERS, DecoderLayerDesc, DecoderLayerGrads, DecoderLayerWeights, EncoderLayerDesc,
                    EncoderLayerGrads, EncoderLayerWeights, Mlp, MlpGrads, PoseOutputs, Pyramid, SdfWeightGrads, SdfWeights, call, lib)
+from ._marshal import (_PINNED_I32, _PreparedBlob, _QueuedCounts, _after_prepared, _check_survivors, _chk, _counts, _p, _rows, _size,
+                       _st, _workspace)
 from .emu_images import WeightImageCache, prepare_batch_table
+from .ops_eval import (_eval_workspace, eval_accum_finish, eval_accum_init, eval_accumulate, eval_hand_joints, eval_mesh, eval_object,
+                       eval_thresholds)
+from .ops_infer import (CONV_ACT, ConvWeight, EncoderPrepared, PoseInferCounts, PosePrepared, _conv_ws, _nhwc_slice, conv2d_nhwc, conv_plan,
+                        encoder_infer, encoder_tensor_table, ik_mano, maxpool2d_nhwc, pose_infer)
+from .ops_mesh import (PreparedMesh, _as_prepared, _InteractionLoss, _iso_grid, _iso_values, _loss_weight, _mask_maps, _Mesh,
+                       _SilhouetteLoss, eval_interaction, eval_silhouette, eval_surface, interaction_loss,
+                       iso_grid_points, iso_refine_grid, iso_surface, mask_edt, mesh_sample_points, mesh_sdf, mesh_sdf_rows,
+                       raster_meshes, raster_overlay, silhouette_loss, silhouette_workspace_views)
 
 _SEED = [0x9E3779B97F4A7C15, 0]
 _WEIGHT_GEN = [0]      # bumped by optimizers that update parameters behind autograd's back (FusedAdamW's HIP kernel does
@@ -118,45 +133,6 @@ def _zero_views(shapes, device):
         views.append(buf[off:off + n].view(sh))
         off += n
     return views
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _workspace(query: str, *dims_dev, least: int = 1):
-    """_workspace("hoisdf_xxx_workspace_bytes", *dims, dev) -> (uint8 scratch tensor of at least `least` bytes, the size to pass on)"""
-    *dims, dev = dims_dev
-    n = getattr(lib(), query)(*dims)
-    if n < 0:
-        raise _lib.HoisdfError(-1, lib().hoisdf_last_error().decode())
-    return torch.empty(max(n, least), device=dev, dtype=torch.uint8), n
-
-
-def _chk(*ts):
-    cur = None
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype not in (torch.float32,):
-            raise RuntimeError("hoisdf_amd ops need float32 CUDA/HIP tensors (no CPU fallback)")
-        if cur is None:
-            cur = torch.cuda.current_device()
-        if t.device.index != cur:       # the C ABI launches on the calling thread's current device and stream
-            raise RuntimeError(f"tensor on cuda:{t.device.index} but the current device is cuda:{cur}: one process per "
-                               "GPU, call torch.cuda.set_device(local_rank) first")
-
-
-def _rows(x: torch.Tensor) -> torch.Tensor:
-    """view as (M, K) with unit inner stride and a uniform row stride"""
-    x2 = x.reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < x2.shape[1]):
-        x2 = x2.contiguous()
-    return x2
 
 
 # ---------------------------------------------------------------------------------------------
@@ -809,10 +785,7 @@ def lattice_candidates(center, cam_intr, bbox, scale: float, bins_n: int):
     return pts, sidx, lidx, counts_h.tolist(), offsets, counts
 
 
-_PINNED_I32 = {}        # B -> free page-locked int32 buffers for the survivor counts (hipHostMalloc per call would cost more than the read)
-
-
-class SdfInferCounts:
+class SdfInferCounts(_QueuedCounts):
     """The queued lattice-survivor count of one field (hoisdf_sdf_infer_count_begin): device counts, their page-locked host
     copy and the event behind the copy.  ``wait()`` blocks the HOST until that copy has executed - the device never drains."""
 
@@ -820,26 +793,13 @@ class SdfInferCounts:
         self.args = (center, cam_intr, bbox, float(scale), int(bins_n))      # keeps the inputs alive until the kernel has run
         B = center.shape[0]
         self.B = B
-        self.counts = torch.empty(B, device=center.device, dtype=torch.int32)
-        free = _PINNED_I32.setdefault(B, [])
-        self.host = free.pop() if free else torch.empty(B, dtype=torch.int32, pin_memory=True)
-        call("hoisdf_sdf_infer_count_begin", _p(center), _p(cam_intr), _p(bbox), float(scale), int(bins_n), B, _p(self.counts),
-             C.c_void_p(self.host.data_ptr()), _st())
-        self.event = torch.cuda.Event()
-        self.event.record()
-        self._list = None
+        super().__init__(B, center.device, lambda counts, host: call(
+            "hoisdf_sdf_infer_count_begin", _p(center), _p(cam_intr), _p(bbox), float(scale), int(bins_n), B, _p(counts), host, _st()))
 
     def matches(self, center, cam_intr, bbox, scale, bins_n) -> bool:
         a = self.args
         return (a[0].data_ptr() == center.data_ptr() and a[1].data_ptr() == cam_intr.data_ptr() and a[2].data_ptr() == bbox.data_ptr()
                 and a[3] == float(scale) and a[4] == int(bins_n) and self.B == center.shape[0])
-
-    def wait(self):
-        if self._list is None:
-            self.event.synchronize()
-            self._list = self.host.tolist()
-            _PINNED_I32[self.B].append(self.host)        # the values are copied out: the buffer can serve the next request
-        return self._list
 
 
 def sdf_infer_count_begin(center, cam_intr, bbox, scale: float, bins_n: int) -> SdfInferCounts:
@@ -867,10 +827,7 @@ def sdf_infer(weights: SdfQueryWeights, pyr: "PyramidNHWC", center, cam_intr, bb
         counts = SdfInferCounts(center, cam_intr, bbox, scale, bins_n)
     cl = counts.wait()
     n = sum(cl)
-    short = [b for b in range(B) if cl[b] < num_points]
-    if short:
-        raise ValueError(f"sdf_infer: sample {short[0]} has only {cl[short[0]]} lattice points inside its bbox, fewer "
-                         f"than num_points={num_points} (the reference fails at main/model.py:348)")
+    _check_survivors(cl, num_points)
     counts_h = (C.c_int32 * B)(*cl)
     w = weights.get()
     assert w.C == pyr.C
@@ -1304,6 +1261,20 @@ def _lin_bwd_weight(dy2, bits, p, x2, dW, db):
     _gemm_bwd_weight(dy2, dy2.stride(0), bits, p if bits is not None else 0.0, x2, x2.stride(0), dW, db, M, N, K)
 
 
+def _encoder_layer_rows(S: int, n_query, n_inter):
+    """-> (nq, ni): the rows of every sample an encoder layer produces (n_query, at most S) and, of those, the rows that get the
+    stack's inter_norm (n_inter, at most nq); None = all"""
+    nq = S if (n_query is None or n_query >= S) else int(n_query)
+    ni = nq if (n_inter is None or n_inter >= nq) else int(n_inter)
+    return nq, ni
+
+
+def _encoder_layer_grad_shapes(E: int, F: int):
+    """the parameter gradients of an encoder layer in the order of hoisdf_encoder_layer_grads: in / out projection (w, b), norm1,
+    linear1, linear2 (w, b), norm2, inter_norm (gamma, beta)"""
+    return [(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E]
+
+
 class _EncoderLayer(torch.autograd.Function):
     """common/nets/transformer.py:286-302 (TransformerEncoderLayer.forward_post) + the stack's ``inter_norm`` of the layer
     output (:117-131) as ONE autograd node: the same kernels as the op-by-op path, but the gradients of tensors with several
@@ -1317,7 +1288,7 @@ class _EncoderLayer(torch.autograd.Function):
         x = x.contiguous()
         _chk(x, w_in, b_in, w_out, b_out, g1, be1, w1, b1, w2, b2, g2, be2, g3, be3)
         B, S, E = x.shape
-        nq = S if (n_query is None or n_query >= S) else int(n_query)
+        nq, ni = _encoder_layer_rows(S, n_query, n_inter)
         full = nq == S
         dev = x.device
         x2d = x.view(B * S, E)
@@ -1366,7 +1337,6 @@ class _EncoderLayer(torch.autograd.Function):
         call("hoisdf_add_layernorm_fwd", _p(x1), _p(f), _p(g2), _p(be2), _p(x2), _p(st[2]), _p(st[3]), M, E, float(eps),
              float(p), s_ln2, _st())
         # inter_norm of the layer output: only rows < n_inter of every sample are ever read by the caller
-        ni = nq if (n_inter is None or n_inter >= nq) else int(n_inter)
         y = torch.empty(B * ni, E, device=dev)
         if ni == nq:
             call("hoisdf_add_layernorm_fwd", _p(x2), None, _p(g3), _p(be3), _p(y), _p(st[4]), _p(st[5]), M, E, float(eps),
@@ -1390,7 +1360,7 @@ class _EncoderLayer(torch.autograd.Function):
         M, F = B * nq, w1.shape[0]
         # one zero-initialised slice for every parameter gradient of the layer
         dw_in, db_in, dw_out, db_out, dg1, dbe1, dw1, db1, dw2, db2, dg2, dbe2, dg3, dbe3 = _zero_views(
-            [(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E], dev)
+            _encoder_layer_grad_shapes(E, F), dev)
         gx2 = None if g_x2 is None else g_x2.contiguous().view(M, E)
         dx2 = torch.empty(M, E, device=dev)
         if g_y is not None:
@@ -1480,8 +1450,7 @@ class _EncoderLayerC(torch.autograd.Function):
         _chk(x, *params)
         assert all(t.is_contiguous() for t in params)
         B, S, E = x.shape
-        nq = S if (n_query is None or n_query >= S) else int(n_query)
-        ni = nq if (n_inter is None or n_inter >= nq) else int(n_inter)
+        nq, ni = _encoder_layer_rows(S, n_query, n_inter)
         d = EncoderLayerDesc(B=B, S=S, E=E, F=w1.shape[0], H=H, n_query=nq, n_inter=ni, eps=eps, drop_p=p,
                              attention=2 if _attn_emulated(nq) else 0, attention_bwd_emulated=int(_emu_bwd()),
                              training=int(any(ctx.needs_input_grad)))
@@ -1519,7 +1488,7 @@ class _EncoderLayerC(torch.autograd.Function):
         B, S, E, F, nq = d.B, d.S, d.E, d.F, d.n_query
         dev = x.device
         # one zero slice for all parameter gradients
-        parts = _zero_views([(3 * E, E), 3 * E, (E, E), E, E, E, (F, E), F, (E, F), E, E, E, E, E], dev)
+        parts = _zero_views(_encoder_layer_grad_shapes(E, F), dev)
         G = EncoderLayerGrads(*[t.data_ptr() for t in parts])
         w = EncoderLayerWeights(*[t.data_ptr() for t in params])
         _EncoderLayerC._images(w, (w_in, w_out, w1, w2), True, B * nq, B * S, E, nq == S)
@@ -1968,136 +1937,6 @@ def mano_gt(mano_param, assets):
     return verts, joints, rot
 
 
-@torch.no_grad()
-def ik_mano(joints, betas, assets):
-    """(f3) the closed-form inverse kinematics of the IK variant + the MANO layer on its result in ONE launch (hoisdf_ik_mano_fwd):
-    joints (H,21,3) metres with the wrist in row 0, or (H,20,3) = joints 1..20 relative to a wrist at the origin; betas (H, >= 10)
-    with unit inner stride (any row stride) or None = zeros; assets as mano_head takes them (hands_mean must be zero) ->
-    pose (H,48) axis-angle, verts (H,778,3) and joints (H,21,3) in metres at the input wrist, valid (H,) int32 = 0 where the palm
-    fit is a reflection (that hand keeps the zero pose)."""
-    joints = joints.contiguous().float()
-    H, nj = joints.shape[0], joints.shape[1]
-    assert joints.dim() == 3 and nj in (20, 21) and joints.shape[2] == 3, tuple(joints.shape)
-    ld = 0
-    if betas is not None:
-        betas = betas.float()
-        assert betas.dim() == 2 and betas.shape[0] == H and betas.shape[1] >= 10, tuple(betas.shape)
-        if betas.stride(1) != 1 or betas.stride(0) < 10:
-            betas = betas[:, :10].contiguous()
-        ld = betas.stride(0)
-    _chk(joints, betas)
-    dev = joints.device
-    pose = torch.empty(H, 48, device=dev, dtype=torch.float32)
-    verts = torch.empty(H, 778, 3, device=dev, dtype=torch.float32)
-    out_joints = torch.empty(H, 21, 3, device=dev, dtype=torch.float32)
-    valid = torch.empty(H, device=dev, dtype=torch.int32)
-    image, tmpl, jreg, w = assets[:4]
-    call("hoisdf_ik_mano_fwd", _p(joints), nj, _p(betas), ld, H, _p(image), _p(tmpl), _p(jreg), _p(w), _p(pose), _p(verts), _p(out_joints),
-         _p(valid), _st())
-    return pose, verts, out_joints, valid
-
-
-# ---------------------------------------------------------------------------------------------
-# (f5) evaluation metrics (csrc/eval.hip, the hoisdf_eval_* entries).  Device tensors in, device tensors out; nothing here
-# synchronises or reads a value back.
-# ---------------------------------------------------------------------------------------------
-def _eval_workspace(B: int, V: int, dev) -> torch.Tensor:
-    return _workspace("hoisdf_eval_workspace_bytes", B, V, dev, least=0)[0]
-
-
-def eval_thresholds(ths, dev) -> torch.Tensor:
-    """thresholds as the device fp64 array the evaluation entries read (a tensor on the device is passed through)"""
-    if torch.is_tensor(ths) and ths.is_cuda and ths.dtype == torch.float64:
-        return ths.contiguous()
-    return torch.as_tensor(np.asarray(ths, dtype=np.float64)).to(dev)
-
-
-@torch.no_grad()
-def eval_object(obj_rot, obj_trans, obj_rot_gt, obj_trans_gt, templates, obj_ids):
-    """hoisdf_eval_object: obj_rot / obj_trans (B,P,3) per-point predictions, obj_rot_gt / obj_trans_gt (B,3), templates (T,V,3),
-    obj_ids (B,) integer template of each sample (negative: not evaluated) -> per-sample (adds, mce, oce, mme) float32 (B,) and
-    used int32 (B,)."""
-    obj_rot, obj_trans = obj_rot.detach().contiguous().float(), obj_trans.detach().contiguous().float()
-    obj_rot_gt, obj_trans_gt = obj_rot_gt.contiguous().float(), obj_trans_gt.contiguous().float()
-    templates = templates.contiguous().float()
-    _chk(obj_rot, obj_trans, obj_rot_gt, obj_trans_gt, templates)
-    B, P = obj_rot.shape[0], obj_rot.shape[1]
-    T, V = templates.shape[0], templates.shape[1]
-    assert obj_rot.shape == (B, P, 3) and obj_trans.shape == (B, P, 3) and obj_rot_gt.shape == (B, 3) and obj_trans_gt.shape == (B, 3)
-    assert templates.dim() == 3 and templates.shape[2] == 3 and obj_ids.shape == (B,), (tuple(templates.shape), tuple(obj_ids.shape))
-    dev = obj_rot.device
-    ids = obj_ids.to(device=dev, dtype=torch.int32).contiguous()
-    adds, mce, oce, mme = (torch.empty(B, device=dev, dtype=torch.float32) for _ in range(4))
-    used = torch.empty(B, device=dev, dtype=torch.int32)
-    ws = _eval_workspace(B, V, dev)
-    call("hoisdf_eval_object", _p(obj_rot), _p(obj_trans), P, _p(obj_rot_gt), _p(obj_trans_gt), _p(templates), T, V, _p(ids), B, _p(adds),
-         _p(mce), _p(oce), _p(mme), _p(used), _p(ws), ws.numel(), _st())
-    return adds, mce, oce, mme, used
-
-
-@torch.no_grad()
-def eval_hand_joints(pred, gt, want_aligned: bool = False, want_transform: bool = False, want_dist: bool = False):
-    """hoisdf_eval_hand_joints: pred / gt (B,J,3) -> per-sample (mje, pamje) float32 (B,), the aligned points (B,J,3) or None, and
-    the fitted similarity (B,13) float64 = c, R row-major, t or None; with want_dist also the per-point distances before and
-    after the alignment, (B,J) each."""
-    pred, gt = pred.detach().contiguous().float(), gt.detach().contiguous().float()
-    _chk(pred, gt)
-    B, J = pred.shape[0], pred.shape[1]
-    assert pred.shape == (B, J, 3) and gt.shape == (B, J, 3), (tuple(pred.shape), tuple(gt.shape))
-    dev = pred.device
-    mje, pamje = torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32)
-    aligned = torch.empty(B, J, 3, device=dev, dtype=torch.float32) if want_aligned else None
-    xf = torch.empty(B, 13, device=dev, dtype=torch.float64) if want_transform else None
-    d0 = torch.empty(B, J, device=dev, dtype=torch.float32) if want_dist else None
-    d1 = torch.empty(B, J, device=dev, dtype=torch.float32) if want_dist else None
-    call("hoisdf_eval_hand_joints", _p(pred), _p(gt), B, J, _p(mje), _p(pamje), _p(aligned), _p(xf), _p(d0), _p(d1), _st())
-    return (mje, pamje, aligned, xf, d0, d1) if want_dist else (mje, pamje, aligned, xf)
-
-
-@torch.no_grad()
-def eval_mesh(pred, gt, thresholds, want_aligned: bool = False):
-    """hoisdf_eval_mesh: pred / gt (B,V,3), thresholds = F-score thresholds (a sequence, or eval_thresholds of one) ->
-    dist_raw, dist_aligned (B,V), fscore, fscore_aligned (B,n_thresh), aligned (B,V,3) or None."""
-    pred, gt = pred.detach().contiguous().float(), gt.detach().contiguous().float()
-    _chk(pred, gt)
-    B, V = pred.shape[0], pred.shape[1]
-    assert pred.shape == (B, V, 3) and gt.shape == (B, V, 3), (tuple(pred.shape), tuple(gt.shape))
-    dev = pred.device
-    th = eval_thresholds(thresholds, dev)
-    nt = th.numel()
-    d0, d1 = torch.empty(B, V, device=dev, dtype=torch.float32), torch.empty(B, V, device=dev, dtype=torch.float32)
-    f0, f1 = torch.empty(B, nt, device=dev, dtype=torch.float32), torch.empty(B, nt, device=dev, dtype=torch.float32)
-    aligned = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_aligned else None
-    ws = _eval_workspace(B, V, dev)
-    call("hoisdf_eval_mesh", _p(pred), _p(gt), B, V, _p(th), nt, _p(d0), _p(d1), _p(f0), _p(f1), _p(aligned), _p(ws), ws.numel(), _st())
-    return d0, d1, f0, f1, aligned
-
-
-def eval_accum_init(V: int, steps: int, dev) -> torch.Tensor:
-    """a zeroed accumulator state (hoisdf_eval_accum_init) for V vertices and `steps` thresholds"""
-    state = _workspace("hoisdf_eval_accum_state_bytes", V, steps, dev, least=0)[0]
-    call("hoisdf_eval_accum_init", _p(state), V, steps, _st())
-    return state
-
-
-@torch.no_grad()
-def eval_accumulate(state, dist, thresholds) -> None:
-    """hoisdf_eval_accum_feed: add dist (B,V) float32 to the state; thresholds = the state's device fp64 array (steps,)"""
-    dist = dist.contiguous()
-    _chk(dist)
-    assert thresholds.is_cuda and thresholds.dtype == torch.float64 and thresholds.is_contiguous()
-    B, V = dist.shape
-    call("hoisdf_eval_accum_feed", _p(state), _p(dist), B, V, _p(thresholds), thresholds.numel(), _st())
-
-
-@torch.no_grad()
-def eval_accum_finish(state, V: int, thresholds) -> torch.Tensor:
-    """hoisdf_eval_accum_finish -> (2 + steps,) float64 on the device: mean EPE, AUC, the PCK curve"""
-    out = torch.empty(2 + thresholds.numel(), device=state.device, dtype=torch.float64)
-    call("hoisdf_eval_accum_finish", _p(state), V, _p(thresholds), thresholds.numel(), _p(out), _st())
-    return out
-
-
 # ---------------------------------------------------------------------------------------------
 # (f4) auxiliary image losses of the encoder outputs
 # ---------------------------------------------------------------------------------------------
@@ -2230,741 +2069,3 @@ def bn_act(x, weight, bias, running_mean, running_var, training: bool, momentum,
         raise RuntimeError("bn_act: training=False normalises with the running statistics and keeps nothing for a backward; "
                            "an input that requires a gradient needs training=True (or torch's batch_norm)")
     return _BnAct.apply(x, weight, bias, residual, running_mean, running_var, bool(training), momentum, float(eps), bool(relu))
-
-
-# ---------------------------------------------------------------------------------------------
-# whole-model inference behind one C entry (include/hoisdf.h hoisdf_pose_*; csrc/pose_infer.hip)
-# ---------------------------------------------------------------------------------------------
-class PosePrepared:
-    """The prepared blob of hoisdf_pose_prepare for one (descriptor, weights) pair: device memory + the descriptor it was built
-    for.  ``version`` counts the builds of the owning model (tests pin that a second frame does not prepare again)."""
-
-    def __init__(self, desc, weights, device, version: int = 0):
-        nbytes = lib().hoisdf_pose_prepared_bytes(C.addressof(desc))
-        if nbytes < 0:
-            raise ValueError(lib().hoisdf_last_error().decode())
-        self.desc, self.version = desc, version
-        self.blob = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        call("hoisdf_pose_prepare", C.addressof(desc), C.addressof(weights), _p(self.blob), nbytes, _st())
-        self.stream = torch.cuda.current_stream(device)
-        self.event = torch.cuda.Event()
-        self.event.record(self.stream)
-
-
-class PoseInferCounts:
-    """hoisdf_pose_infer_begin: the queued survivor counts of both fields (2 B words: hand, object), their page-locked host copy and
-    the event behind the copy - as SdfInferCounts, for the whole-model entry."""
-
-    def __init__(self, desc, root, ocen, cam_intr, bbox_hand, bbox_obj):
-        self.args = tuple(t.contiguous() for t in (root, ocen, cam_intr, bbox_hand, bbox_obj))
-        _chk(*self.args)
-        B = root.shape[0]
-        self.B = B
-        self.counts = torch.empty(2 * B, device=root.device, dtype=torch.int32)
-        free = _PINNED_I32.setdefault(2 * B, [])
-        self.host = free.pop() if free else torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
-        call("hoisdf_pose_infer_begin", C.addressof(desc), *(_p(t) for t in self.args), _p(self.counts), C.c_void_p(self.host.data_ptr()), _st())
-        self.event = torch.cuda.Event()
-        self.event.record()
-        self._list = None
-
-    def wait(self):
-        if self._list is None:
-            self.event.synchronize()
-            self._list = self.host.tolist()
-            _PINNED_I32[2 * self.B].append(self.host)
-        return self._list
-
-
-@torch.no_grad()
-def pose_infer(prepared: PosePrepared, pyr: "PyramidNHWC", root, ocen, cam_intr, bbox_hand, bbox_obj, counts: Optional[PoseInferCounts] = None,
-               side_stream=None, debug: bool = False):
-    """hoisdf_pose_infer: the eval forward of everything after the image encoder in ONE C-ABI call -> dict of the ``*_out`` tensors
-    (with ``debug`` also the selected points and their SDF values; with the descriptor's ``ik_solve`` also ``ik_joints_out`` /
-    ``ik_verts_out`` / ``ik_pose_out`` / ``ik_valid_out``, root-relative).  Raises ValueError when a sample has fewer lattice survivors
-    than requested points (nothing is launched then)."""
-    d = prepared.desc
-    dev = root.device
-    if counts is None:
-        counts = PoseInferCounts(d, root, ocen, cam_intr, bbox_hand, bbox_obj)
-    root, ocen, cam_intr, bbox_hand, bbox_obj = counts.args
-    B, nh, no = d.B, d.num_samp_hand, d.num_samp_obj
-    e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    out = {"hand_joints_out": e(B, 20, 3), "obj_rot_out": e(B, no, 3), "obj_trans_out": e(B, no, 3)}
-    c_names = {}                 # this dict's key -> the field of hoisdf_pose_outputs, where they differ
-    if d.use_inverse_kinematics:
-        out["mano_shape_out"] = e(B, 10)
-        if d.ik_solve:           # the IK post-process as the call's last launch, under the keys engine.Tester.predict uses
-            out.update(ik_joints_out=e(B, 21, 3), ik_verts_out=e(B, 778, 3), ik_pose_out=e(B, 48),
-                       ik_valid_out=torch.empty(B, device=dev, dtype=torch.int32))
-            c_names = {"ik_joints_out": "mano_joints_out", "ik_verts_out": "mano_mesh_out", "ik_pose_out": "mano_pose_out"}
-    else:
-        out["mano_mesh_out"], out["mano_joints_out"] = e(B, 778, 3), e(B, 21, 3)
-    if debug:
-        out.update(hand_points_out=e(B, nh, 3), obj_points_out=e(B, no, 3), hand_sdf_out=e(B, nh), obj_sdf_out=e(B, no))
-    cl = counts.wait()          # the one host read of the path: everything that does not need the counts is done
-    counts_h = (C.c_int32 * (2 * B))(*cl)
-    for kind, n, part in (("hand", nh, cl[:B]), ("obj", no, cl[B:])):
-        short = [b for b in range(B) if part[b] < n]
-        if short:
-            raise ValueError(f"sdf_infer({kind}): sample {short[0]} has only {part[short[0]]} lattice points inside its bbox, fewer "
-                             f"than num_points={n} (the reference fails at main/model.py:348)")
-    nbytes = lib().hoisdf_pose_infer_workspace(C.addressof(d), C.addressof(counts_h))
-    if nbytes < 0:
-        raise ValueError(lib().hoisdf_last_error().decode())
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    o = PoseOutputs(**{c_names.get(k, k): v.data_ptr() for k, v in out.items()})
-    cur = torch.cuda.current_stream(dev)
-    if prepared.stream != cur:
-        cur.wait_event(prepared.event)
-    s = pyr.struct()
-    call("hoisdf_pose_infer", C.addressof(d), _p(prepared.blob), C.byref(s), _p(root), _p(ocen), _p(cam_intr), _p(bbox_hand), _p(bbox_obj),
-         _p(counts.counts), C.addressof(counts_h), C.addressof(o), _p(ws), nbytes,
-         None if side_stream is None else C.c_void_p(side_stream.cuda_stream), _st())
-    return out          # (the call returns with the current stream ordered behind the side stream's work: no record_stream needed)
-
-
-# ---------------------------------------------------------------------------------------------
-# convolution forward on channels-last maps (include/hoisdf.h hoisdf_conv*; csrc/conv.hip): exact f32, evaluation only
-# ---------------------------------------------------------------------------------------------
-CONV_ACT = {None: 0, "none": 0, "relu": 1, "sigmoid": 2}
-
-
-class ConvWeight:
-    """A convolution's weight packed once for the implicit-GEMM kernel (hoisdf_conv_pack_weight), an evaluation-mode BatchNorm folded
-    in when ``bn`` = (gamma, beta, running_mean, running_var, eps) is given.  ``w``: [C_out][C_in][KH][KW], or ConvTranspose2d's
-    [C_in][C_out][4][4] with ``transposed``."""
-
-    def __init__(self, w, bias=None, bn=None, transposed: bool = False):
-        g, be, mu, var, eps = bn if bn is not None else (None, None, None, None, 0.0)
-        ts = [t if t is None else t.detach().contiguous() for t in (w, bias, g, be, mu, var)]
-        _chk(*ts)
-        self.transposed = bool(transposed)
-        self.C_out, self.C_in = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
-        self.KH, self.KW = w.shape[2], w.shape[3]
-        n = lib().hoisdf_conv_packed_floats(self.C_out, self.C_in, self.KH, self.KW)
-        self.packed = torch.empty(n, device=w.device, dtype=torch.float32)
-        self.bias = torch.empty((self.C_out + 3) // 4 * 4, device=w.device, dtype=torch.float32)
-        call("hoisdf_conv_pack_weight", *(_p(t) for t in ts), float(eps), self.C_out, self.C_in, self.KH, self.KW, int(self.transposed),
-             _p(self.packed), _p(self.bias), _st())
-
-
-def conv_plan(M: int, C_out: int, K: int, classes: int = 1):
-    """(tile, splitk) the convolution takes for M output rows, C_out columns and a contraction of K (classes = 4: transposed)"""
-    tile, splitk = C.c_int(0), C.c_int(0)
-    call("hoisdf_conv_plan", M, C_out, K, classes, C.addressof(tile), C.addressof(splitk))
-    return tile.value, splitk.value
-
-
-def _conv_ws(M, C_out, K, classes, device):
-    n = lib().hoisdf_conv_workspace_bytes(M, C_out, K, classes)
-    if n < 0:
-        raise ValueError(lib().hoisdf_last_error().decode())
-    return (torch.empty(n, device=device, dtype=torch.uint8) if n else None), n
-
-
-def _nhwc_slice(x):
-    """a channels-last map or a channel slice of one: [B][H][W][C] with unit channel stride and dense pixels -> row stride"""
-    B, H, W, Cc = x.shape
-    ld = x.stride(2)
-    if x.stride(3) != 1 or ld < Cc or x.stride(1) != W * ld or x.stride(0) != H * W * ld:
-        raise ValueError("expected an NHWC map (or a channel slice of one) with dense pixels")
-    return ld
-
-
-@torch.no_grad()
-def conv2d_nhwc(x, w: ConvWeight, stride: int = 1, pad: int = 0, act=None, residual=None, out=None, c_off: int = 0):
-    """y = act(conv(x) + bias (+ residual)) on NHWC maps; ``x`` / ``residual`` / ``out`` may be channel slices of wider maps, or
-    ``out`` a wider map whose channels [c_off, c_off + C_out) are written.  ConvTranspose2d(4, 2, 1) when ``w`` was packed transposed."""
-    _chk(x, residual, out)
-    B, H, W, _ = x.shape
-    ldx = _nhwc_slice(x)
-    if w.transposed:
-        OH, OW, M, K, classes = 2 * H, 2 * W, B * H * W, 4 * w.C_in, 4
-    else:
-        OH, OW = (H + 2 * pad - w.KH) // stride + 1, (W + 2 * pad - w.KW) // stride + 1
-        M, K, classes = B * OH * OW, w.KH * w.KW * w.C_in, 1
-    if out is None:
-        out = torch.empty(B, OH, OW, w.C_out, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, OH, OW) or c_off < 0 or out.shape[3] < c_off + w.C_out or x.shape[3] != w.C_in:
-        raise ValueError(f"conv2d_nhwc: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit the weight")
-    ldy = _nhwc_slice(out)
-    ws, nws = _conv_ws(M, w.C_out, K, classes, x.device)
-    if w.transposed:
-        if residual is not None:
-            raise ValueError("the transposed convolution takes no residual")
-        call("hoisdf_conv_transpose2d_fwd", _p(x), ldx, _p(w.packed), _p(w.bias), _p(out), ldy, c_off, B, H, W, w.C_in, w.C_out, CONV_ACT[act],
-             _p(ws), nws, _st())
-    else:
-        ldr = 0 if residual is None else _nhwc_slice(residual)
-        call("hoisdf_conv2d_fwd", _p(x), ldx, _p(w.packed), _p(w.bias), _p(residual), ldr, _p(out), ldy, c_off, B, H, W, w.C_in, w.C_out, w.KH,
-             w.KW, stride, pad, CONV_ACT[act], _p(ws), nws, _st())
-    return out[..., c_off:c_off + w.C_out]
-
-
-@torch.no_grad()
-def maxpool2d_nhwc(x):
-    """MaxPool2d(3, 2, 1) of an NHWC map"""
-    _chk(x)
-    B, H, W, Cc = x.shape
-    y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, device=x.device, dtype=torch.float32)
-    call("hoisdf_maxpool2d_fwd", _p(x), _nhwc_slice(x), _p(y), Cc, B, H, W, Cc, _st())
-    return y
-
-
-# ---------------------------------------------------------------------------------------------
-# the image encoder in evaluation mode behind one C entry (include/hoisdf.h hoisdf_encoder_*; csrc/encoder_infer.hip)
-# ---------------------------------------------------------------------------------------------
-def encoder_tensor_table(desc):
-    """[(checkpoint key, numel)] in the order hoisdf_encoder_prepare takes the tensors"""
-    L, d = lib(), C.addressof(desc)
-    n = L.hoisdf_encoder_tensor_count(d)
-    if n < 0:
-        raise ValueError(L.hoisdf_last_error().decode())
-    return [(L.hoisdf_encoder_tensor_name(d, i).decode(), L.hoisdf_encoder_tensor_numel(d, i)) for i in range(n)]
-
-
-class EncoderPrepared:
-    """The prepared blob of hoisdf_encoder_prepare (BatchNorm folds + packed weights) for one (descriptor, weights) pair and the
-    workspace of its frames.  ``tensors``: checkpoint key -> tensor, for every key of the table."""
-
-    def __init__(self, desc, tensors, device, version: int = 0):
-        table = encoder_tensor_table(desc)
-        keep = []
-        for name, numel in table:
-            t = tensors[name].detach().float().contiguous()
-            if t.numel() != numel:
-                raise ValueError(f"{name}: {t.numel()} elements, the table has {numel}")
-            keep.append(t)
-        _chk(*keep)
-        nbytes = lib().hoisdf_encoder_prepared_bytes(C.addressof(desc))
-        nws = lib().hoisdf_encoder_infer_workspace(C.addressof(desc))
-        if nbytes < 0 or nws < 0:
-            raise ValueError(lib().hoisdf_last_error().decode())
-        self.desc, self.version = desc, version
-        self.blob = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        self.workspace = torch.empty(nws, device=device, dtype=torch.uint8)
-        ptrs = (C.c_void_p * len(keep))(*(t.data_ptr() for t in keep))
-        call("hoisdf_encoder_prepare", C.addressof(desc), ptrs, len(keep), _p(self.blob), nbytes, _st())
-        self.stream = torch.cuda.current_stream(device)
-        self.event = torch.cuda.Event()
-        self.event.record(self.stream)
-        shape = Pyramid()
-        call("hoisdf_encoder_pyramid_shape", C.addressof(desc), C.byref(shape))
-        self.level_shapes = [(desc.B, shape.H[i], shape.W[i], shape.C[i]) for i in range(shape.n_levels)]
-
-
-@torch.no_grad()
-def encoder_infer(prepared: EncoderPrepared, img, want_aux: bool = True):
-    """hoisdf_encoder_infer: ``img`` (B, 3, H, W) as the dataset yields it (a channels_last tensor is passed without a copy, anything
-    else through one permute-copy) -> (PyramidNHWC, aux NHWC [B][H / 2][W / 2][3] or None)"""
-    d = prepared.desc
-    if tuple(img.shape) != (d.B, 3, d.img_h, d.img_w):
-        raise ValueError(f"encoder_infer: image {tuple(img.shape)}, prepared for {(d.B, 3, d.img_h, d.img_w)}")
-    x = img.permute(0, 2, 3, 1)
-    if not x.is_contiguous():
-        x = x.contiguous()
-    _chk(x)
-    dev = x.device
-    levels = [torch.empty(s, device=dev, dtype=torch.float32) for s in prepared.level_shapes]
-    aux = torch.empty(d.B, d.img_h // 2, d.img_w // 2, 3, device=dev, dtype=torch.float32) if want_aux else None
-    cur = torch.cuda.current_stream(dev)
-    if prepared.stream != cur:
-        cur.wait_event(prepared.event)
-    ptrs = (C.c_void_p * len(levels))(*(t.data_ptr() for t in levels))
-    call("hoisdf_encoder_infer", C.addressof(d), _p(prepared.blob), _p(x), ptrs, _p(aux), _p(prepared.workspace), prepared.workspace.numel(), _st())
-    return PyramidNHWC(levels), aux
-
-
-# ---------------------------------------------------------------------------------------------
-# SDF supervision from meshes (csrc/mesh_sdf.hip, the hoisdf_mesh_* entries).  No gradient: these are labels.
-# ---------------------------------------------------------------------------------------------
-def _counts(n, B: int, dev, what: str):
-    """per-sample counts -> int32 (B,) on the device (None stays None)"""
-    if n is None:
-        return None
-    n = torch.as_tensor(n).to(dev, torch.int32).contiguous()
-    if n.shape != (B,):
-        raise ValueError(f"{what} {tuple(n.shape)}: one count per sample ({B},)")
-    return n
-
-
-class _Mesh:
-    """A batch of meshes as the C ABI takes it: verts (B, V, 3) -> float32; faces (F, 3) shared by the batch or (B, F, 3) per sample,
-    any integer dtype -> int32; n_faces (B,) = the rows of each sample that count (None: all F) -> int32.  ``B`` given: the batch the
-    mesh must match; ``what`` opens the messages.  ``desc`` is the hoisdf_mesh; the tensors it points to live with this object."""
-
-    def __init__(self, verts, faces, n_faces, B: Optional[int], what: str):
-        verts = verts.detach().contiguous().float()
-        _chk(verts)
-        if verts.dim() != 3 or verts.shape[2] != 3 or (B is not None and verts.shape[0] != B):
-            raise ValueError(f"{what} vertices {tuple(verts.shape)}: one (V, 3) mesh per sample" + ("" if B is None else f" of {B}"))
-        dev, B = verts.device, verts.shape[0]
-        faces = faces.to(dev, torch.int32).contiguous()
-        if faces.dim() not in (2, 3) or faces.shape[-1] != 3 or (faces.dim() == 3 and faces.shape[0] != B):
-            raise ValueError(f"{what} faces {tuple(faces.shape)}: (F, 3) or ({B}, F, 3)")
-        self.verts, self.faces, self.n_faces = verts, faces, _counts(n_faces, B, dev, f"{what} face counts")
-        self.B, self.V, self.F = B, verts.shape[1], faces.shape[-2]
-        self.stride = 0 if faces.dim() == 2 else 3 * self.F
-        self.desc = _lib.Mesh(verts=verts.data_ptr(), faces=faces.data_ptr(), n_faces=None if self.n_faces is None else self.n_faces.data_ptr(),
-                              face_batch_stride=self.stride, V=self.V, max_faces=self.F)
-
-
-class PreparedMesh(_Mesh):
-    """hoisdf_mesh_prepare on a batch of meshes: verts (B, V, 3); faces (F, 3) shared by the batch or (B, F, 3) per sample, any
-    integer dtype; n_faces (B,) = the rows of each sample that count (None: all F).  Holds tris / area / cdf / box on the device."""
-
-    def __init__(self, verts, faces, n_faces=None):
-        super().__init__(verts, faces, n_faces, None, "mesh:")
-        B, F, dev = self.B, self.F, self.verts.device
-        self.tris = torch.empty(B, F, 12, device=dev, dtype=torch.float32)
-        self.area = torch.empty(B, F, device=dev, dtype=torch.float32)
-        self.cdf = torch.empty(B, F, device=dev, dtype=torch.float32)
-        self.box = torch.empty(B, 8, device=dev, dtype=torch.float32)
-        call("hoisdf_mesh_prepare", _p(self.verts), B, self.V, _p(self.faces), self.stride, _p(self.n_faces), F, _p(self.tris),
-             _p(self.area), _p(self.cdf), _p(self.box), _st())
-
-
-def _as_prepared(verts, faces, n_faces) -> PreparedMesh:
-    return verts if isinstance(verts, PreparedMesh) else PreparedMesh(verts, faces, n_faces)
-
-
-@torch.no_grad()
-def mesh_sdf(points, verts, faces=None, n_faces=None, vert_label=None, out=None, extras: bool = False):
-    """Exact signed distance of points (B, N, >= 3) (xyz first, unit inner stride) to the mesh of their sample; ``verts`` may be a
-    PreparedMesh.  vert_label (V,) shared or (B, V) ints: also the label of the nearest vertex-corner.  ``out`` (B, N) float32 view
-    with any element stride inside a row block (e.g. ``rows[..., 3]``) receives the distances in place.
-    -> sdf (B, N) [, label (B, N) int32]; with extras a dict: sdf, face, bary, winding [, label]."""
-    m = _as_prepared(verts, faces, n_faces)
-    if points.dim() != 3 or points.shape[0] != m.B or points.shape[2] < 3:
-        raise ValueError(f"mesh_sdf: points {tuple(points.shape)} for {m.B} meshes")
-    if points.stride(2) != 1 or points.stride(0) != points.shape[1] * points.stride(1) or points.dtype != torch.float32:
-        points = points.float().contiguous()
-    _chk(points)
-    B, N, dev = m.B, points.shape[1], points.device
-    if out is None:
-        out = torch.empty(B, N, device=dev, dtype=torch.float32)
-    if out.shape != (B, N) or out.dtype != torch.float32 or (N and out.stride(0) != N * out.stride(1)) or out.stride(1) < 1:
-        raise ValueError("mesh_sdf: out must be a (B, N) float32 view whose rows follow each other")
-    _chk(out)
-    lab = stride = None
-    if vert_label is not None:
-        lab = vert_label.to(dev, torch.int32).contiguous()
-        if lab.shape not in ((m.V,), (B, m.V)):
-            raise ValueError(f"mesh_sdf: vert_label {tuple(lab.shape)} for {m.V} vertices")
-        stride = 0 if lab.dim() == 1 else m.V
-    label = torch.empty(B, N, device=dev, dtype=torch.int32) if lab is not None else None
-    face = torch.empty(B, N, device=dev, dtype=torch.int32) if extras else None
-    bary = torch.empty(B, N, 3, device=dev, dtype=torch.float32) if extras else None
-    wind = torch.empty(B, N, device=dev, dtype=torch.float32) if extras else None
-    call("hoisdf_mesh_sdf", _p(points), points.stride(1), B, N, _p(m.tris), _p(m.box), _p(m.n_faces), m.F, _p(lab), stride or 0,
-         _p(out), out.stride(1) if N else 1, _p(face), _p(bary), _p(wind), _p(label), _st())
-    if extras:
-        r = {"sdf": out, "face": face, "bary": bary, "winding": wind}
-        if label is not None:
-            r["label"] = label
-        return r
-    return out if label is None else (out, label)
-
-
-@torch.no_grad()
-def mesh_sample_points(verts, faces=None, n_faces=None, n_points: int = 0, sigma=(0.01, 0.003), uniform_every: int = 16,
-                       pad: float = 0.05, seed: int = 0, with_faces: bool = False):
-    """n_points query points per sample around the mesh (``verts`` may be a PreparedMesh): near-surface with sigma[0] / sigma[1],
-    every ``uniform_every``-th uniform in the box padded by ``pad``; a pure function of (seed, sample, index).
-    -> points (B, n_points, 3) [, face (B, n_points) int32: the face a near-surface point started from, -1 for a box point]"""
-    m = _as_prepared(verts, faces, n_faces)
-    dev = m.tris.device
-    pts = torch.empty(m.B, n_points, 3, device=dev, dtype=torch.float32)
-    face = torch.empty(m.B, n_points, device=dev, dtype=torch.int32) if with_faces else None
-    call("hoisdf_mesh_sample_points", _p(m.tris), _p(m.cdf), _p(m.box), _p(m.n_faces), m.F, m.B, n_points, float(sigma[0]),
-         float(sigma[1]), int(uniform_every), float(pad), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(pts), 3, _p(face), _st())
-    return (pts, face) if with_faces else pts
-
-
-@torch.no_grad()
-def mesh_sdf_rows(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces, hand_vert_label, n_hand: int, n_obj: int,
-                  sigma=(0.01, 0.003), uniform_every: int = 16, pad: float = 0.05, clamp: float = 0.05, seed: int = 0):
-    """hoisdf_mesh_sdf_rows: hand mesh (B, Vh, 3) with shared faces (Fh, 3), object mesh (B, Vo, 3) with faces (B, Fo, 3) (or
-    shared (Fo, 3)) and face counts obj_n_faces (B,) or None -> rows (B, n_hand + n_obj, 6) = [x y z sdf_hand sdf_obj label]."""
-    mh = _Mesh(hand_verts, hand_faces, None, None, "mesh_sdf_rows: hand")
-    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "mesh_sdf_rows: object")
-    dev, B = mh.verts.device, mh.B
-    lab = hand_vert_label.to(dev, torch.int32).contiguous()
-    if lab.shape != (mh.V,) or mh.faces.dim() != 2:
-        raise ValueError("mesh_sdf_rows: hand faces (Fh, 3) shared by the batch, one label per hand vertex")
-    ws, nws = _workspace("hoisdf_mesh_sdf_rows_workspace_bytes", B, mh.F, mo.F, dev)
-    rows = torch.empty(B, n_hand + n_obj, 6, device=dev, dtype=torch.float32)
-    call("hoisdf_mesh_sdf_rows", C.addressof(mh.desc), C.addressof(mo.desc), _p(lab), B, n_hand, n_obj, float(sigma[0]), float(sigma[1]),
-         int(uniform_every), float(pad), float(clamp), int(seed) & 0x7FFFFFFFFFFFFFFF, _p(rows), 6, _p(ws), nws, _st())
-    return rows
-
-
-# ---------------------------------------------------------------------------------------------
-# Hand-object interaction metrics (csrc/interact.hip, hoisdf_eval_interaction).  No gradient: these are evaluation numbers.
-# ---------------------------------------------------------------------------------------------
-@torch.no_grad()
-def eval_interaction(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=None, obj_n_verts=None, contact_dist: float = 0.005,
-                     voxel: float = 0.005, want_mask: bool = False, hand_n_faces=None):
-    """hoisdf_eval_interaction: hand mesh (B, Vh, 3) with shared faces (Fh, 3) (per-sample (B, Fh, 3) with counts hand_n_faces (B,)
-    is taken too), object mesh (B, Vo, 3) with faces (B, Fo, 3) (or
-    shared (Fo, 3)), face counts obj_n_faces (B,) and vertex counts obj_n_verts (B,) or None; one frame, metres -> a dict of
-    per-sample tensors: pen_hand, pen_obj, min_dist, volume float32 (B,); contact_verts, in_contact, inside_count int32 (B,);
-    grid float32 (B, 8) = lo xyz, cell xyz, the bits of n_x | n_y << 8 | n_z << 16, 0; with want_mask also inside uint8
-    (B, 64^3): 1 where cell ix + n_x (iy + n_y iz) lies in both meshes, zero from n_x n_y n_z on.  want_mask may be that tensor:
-    it is written in place, and its bytes from n_x n_y n_z on are left as they are."""
-    mh = _Mesh(hand_verts, hand_faces, hand_n_faces, None, "eval_interaction: hand")
-    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "eval_interaction: object")
-    dev, B = mh.verts.device, mh.B
-    ov = _counts(obj_n_verts, B, dev, "eval_interaction: obj_n_verts")
-    ws, nws = _workspace("hoisdf_eval_interaction_workspace_bytes", B, mh.V, mh.F, mo.V, mo.F, dev)
-    f32 = dict(device=dev, dtype=torch.float32)
-    i32 = dict(device=dev, dtype=torch.int32)
-    out = {"pen_hand": torch.empty(B, **f32), "pen_obj": torch.empty(B, **f32), "min_dist": torch.empty(B, **f32),
-           "contact_verts": torch.empty(B, **i32), "in_contact": torch.empty(B, **i32), "volume": torch.empty(B, **f32),
-           "inside_count": torch.empty(B, **i32), "grid": torch.empty(B, 8, **f32)}
-    cells = _lib.CONSTANTS["INTERACT_MAX_GRID"] ** 3
-    mask = None
-    if torch.is_tensor(want_mask):
-        mask = want_mask
-        if mask.shape != (B, cells) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev:
-            raise ValueError(f"eval_interaction: the mask must be a contiguous uint8 tensor of shape ({B}, {cells}) on {dev}")
-    elif want_mask:
-        mask = torch.zeros(B, cells, device=dev, dtype=torch.uint8)
-    call("hoisdf_eval_interaction", C.addressof(mh.desc), C.addressof(mo.desc), _p(ov), B, float(contact_dist), float(voxel), _p(out["pen_hand"]),
-         _p(out["pen_obj"]), _p(out["min_dist"]), _p(out["contact_verts"]), _p(out["in_contact"]), _p(out["volume"]),
-         _p(out["inside_count"]), _p(mask), _p(out["grid"]), _p(ws), nws, _st())
-    if mask is not None:
-        out["inside"] = mask
-    return out
-
-
-# ---------------------------------------------------------------------------------------------
-# Hand-object interaction loss (csrc/interact_loss.hip, hoisdf_interaction_loss_fwd / _bwd): repulsion and attraction with gradients
-# to both vertex arrays.
-# ---------------------------------------------------------------------------------------------
-def _loss_weight(w, B: int, V: int, dev, what: str):
-    """a per-vertex weight array -> (tensor or None, batch stride in elements): (V,) shared by the batch, (B, V) per sample"""
-    if w is None:
-        return None, 0
-    w = torch.as_tensor(w).detach().to(dev, torch.float32).contiguous()
-    if w.shape not in ((V,), (B, V)):
-        raise ValueError(f"interaction_loss: {what} {tuple(w.shape)}: ({V},) or ({B}, {V})")
-    return w, (0 if w.dim() == 1 else V)
-
-
-class _InteractionLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, hand_verts, obj_verts, mh, mo, ov, weights, alpha):
-        # mh / mo: the two meshes marshalled from (detached copies of) hand_verts / obj_verts, which are here for the graph alone
-        dev, B = mh.verts.device, mh.B
-        ws, nws = _workspace("hoisdf_interaction_loss_workspace_bytes", B, mh.V, mh.F, mo.V, mo.F, dev)
-        out = [torch.empty(B, device=dev, dtype=torch.float32) for _ in range(3)]
-        (wr, sr), (wa, sa), (wo, so) = weights
-        common = (C.addressof(mh.desc), C.addressof(mo.desc), _p(ov), B, _p(wr), sr, _p(wa), sa, _p(wo), so, float(alpha))
-        call("hoisdf_interaction_loss_fwd", *common, _p(out[0]), _p(out[1]), _p(out[2]), _p(ws), nws, _st())
-        # the backward reads the workspace and every input again: all of them (the meshes hold the tensors their descriptors point
-        # to) stay alive, and unchanged, with the context
-        ctx.keep = (mh, mo, ov, wr, wa, wo, ws)
-        ctx.common, ctx.nws = common, nws
-        ctx.set_materialize_grads(False)
-        return tuple(out)
-
-    @staticmethod
-    def backward(ctx, g_rep_hand, g_att, g_rep_obj):
-        mh, mo = ctx.keep[0], ctx.keep[1]
-        gs = [None if g is None else g.contiguous().float() for g in (g_rep_hand, g_att, g_rep_obj)]
-        _chk(*gs)
-        d_hand, d_obj = torch.empty_like(mh.verts), torch.empty_like(mo.verts)
-        call("hoisdf_interaction_loss_bwd", *ctx.common, _p(gs[0]), _p(gs[1]), _p(gs[2]), _p(d_hand), _p(d_obj), _p(ctx.keep[-1]), ctx.nws, _st())
-        return d_hand, d_obj, None, None, None, None, None
-
-
-def interaction_loss(hand_verts, hand_faces, obj_verts, obj_faces, obj_n_faces=None, obj_n_verts=None, rep_w_hand=None,
-                     att_w_hand=None, rep_w_obj=None, alpha: float = 0.01, hand_n_faces=None):
-    """hoisdf_interaction_loss_fwd / _bwd: the meshes as ``eval_interaction`` takes them (one frame, metres); rep_w_hand, att_w_hand
-    (Vh,) or (B, Vh) and rep_w_obj (Vo,) or (B, Vo) per-vertex weights, None = ones; alpha: the length at which the attraction
-    saturates -> (rep_hand, att, rep_obj), each (B,): the weighted means of max(0, -sdf_obj) and alpha tanh(max(0, sdf_obj) / alpha)
-    over the hand vertices and of max(0, -sdf_hand) over the object's vertices that count.  Gradients flow to hand_verts and obj_verts
-    only (the envelope rule of include/hoisdf.h "interaction loss"); order-fixed: two calls give the same bits."""
-    mh = _Mesh(hand_verts, hand_faces, hand_n_faces, None, "interaction_loss: hand")
-    mo = _Mesh(obj_verts, obj_faces, obj_n_faces, mh.B, "interaction_loss: object")
-    _chk(hand_verts, obj_verts)                              # the gradients go back as float32: no other dtype is taken
-    dev, B = mh.verts.device, mh.B
-    ov = _counts(obj_n_verts, B, dev, "interaction_loss: obj_n_verts")
-    weights = (_loss_weight(rep_w_hand, B, mh.V, dev, "rep_w_hand"), _loss_weight(att_w_hand, B, mh.V, dev, "att_w_hand"),
-               _loss_weight(rep_w_obj, B, mo.V, dev, "rep_w_obj"))
-    return _InteractionLoss.apply(hand_verts, obj_verts, mh, mo, ov, weights, float(alpha))
-
-
-# ---------------------------------------------------------------------------------------------
-# Surface from a sampled field (csrc/isosurf.hip, the hoisdf_iso_* entries and hoisdf_eval_surface).  No gradient.
-# ---------------------------------------------------------------------------------------------
-def _iso_grid(grid, n: int):
-    grid = grid.contiguous().float()
-    _chk(grid)
-    if grid.dim() != 2 or grid.shape[1] != 8:
-        raise ValueError(f"iso: grid {tuple(grid.shape)} must be (B, 8) = lo xyz, cell xyz, 0, 0")
-    if not 2 <= int(n) <= _lib.CONSTANTS["ISO_MAX_GRID"]:
-        raise ValueError(f"iso: n={n} (2 .. {_lib.CONSTANTS['ISO_MAX_GRID']})")
-    return grid, grid.shape[0], int(n) ** 3
-
-
-def _iso_values(values, B: int, N: int, what: str):
-    """(B, n^3) float32 view whose rows follow each other, any element stride (a column of a wider row block) -> (view, ld)"""
-    if values.dim() != 2 or values.shape != (B, N) or values.dtype != torch.float32 or values.stride(1) < 1 or \
-            (B > 1 and values.stride(0) != N * values.stride(1)):
-        values = values.reshape(B, N).float().contiguous()
-    _chk(values)
-    return values, values.stride(1)
-
-
-@torch.no_grad()
-def iso_grid_points(grid, n: int, with_sample_idx: bool = True):
-    """grid (B, 8) -> points (B n^3, 3) [, sample_idx (B n^3,) int32]: the node positions as rows for sdf_query"""
-    grid, B, N = _iso_grid(grid, n)
-    pts = torch.empty(B * N, 3, device=grid.device, dtype=torch.float32)
-    idx = torch.empty(B * N, device=grid.device, dtype=torch.int32) if with_sample_idx else None
-    call("hoisdf_iso_grid_points", _p(grid), int(n), B, _p(pts), _p(idx), _st())
-    return (pts, idx) if with_sample_idx else pts
-
-
-@torch.no_grad()
-def iso_refine_grid(values, grid, n: int, iso: float = 0.0, pad_cells: int = 1, n_out: Optional[int] = None):
-    """values (B, n^3) on grid (B, 8) -> the (B, 8) grid of n_out nodes over the index box of the nodes below iso, grown by
-    pad_cells and clipped to the coarse grid (a sample without such a node: the coarse grid re-divided).  No host read."""
-    grid, B, N = _iso_grid(grid, n)
-    values, ld = _iso_values(values, B, N, "iso_refine_grid")
-    out = torch.empty(B, 8, device=grid.device, dtype=torch.float32)
-    call("hoisdf_iso_refine_grid", _p(values), ld, _p(grid), int(n), B, float(iso), int(pad_cells), int(n if n_out is None else n_out),
-         _p(out), _st())
-    return out
-
-
-@torch.no_grad()
-def iso_surface(values, grid, n: int, iso: float = 0.0, max_verts: Optional[int] = None, max_faces: Optional[int] = None,
-                out_scale: Optional[float] = None, out_shift=None):
-    """hoisdf_iso_extract: values (B, n^3) on grid (B, 8) -> (verts (B, max_verts, 3), faces (B, max_faces, 3) int32, n_verts (B,),
-    n_faces (B,) int32): the counts NEEDED; rows beyond them are not written (zero here), and a sample whose count exceeds a
-    capacity is overflowed - its written faces keep their true vertex ids.  With both capacities given nothing synchronises;
-    a capacity left None is sized from one count-only call and one read of the counts (exact allocation).  out_scale /
-    out_shift (B, 3): the stored vertex is x * out_scale + out_shift."""
-    grid, B, N = _iso_grid(grid, n)
-    values, ld = _iso_values(values, B, N, "iso_surface")
-    dev = grid.device
-    shift = None
-    if out_shift is not None or out_scale is not None:
-        shift = torch.zeros(B, 3, device=dev, dtype=torch.float32) if out_shift is None else out_shift.reshape(B, 3).contiguous().float()
-        _chk(shift)
-    scale = 1.0 if out_scale is None else float(out_scale)
-    ws, nws = _workspace("hoisdf_iso_extract_workspace_bytes", B, int(n), dev)
-    nv =torch.zeros(B, device=dev, dtype=torch.int32)
-    nf = torch.zeros(B, device=dev, dtype=torch.int32)
-
-    def run(verts, faces, mv, mf):
-        call("hoisdf_iso_extract", _p(values), ld, _p(grid), int(n), B, float(iso), scale, _p(shift), _p(verts), mv, _p(faces), mf,
-             _p(nv), _p(nf), _p(ws), nws, _st())
-
-    if max_verts is None or max_faces is None:
-        run(None, None, 0, 0)
-        counts = torch.stack([nv, nf]).amax(1).tolist() if B else [0, 0]      # the one sized read-back
-        max_verts = counts[0] if max_verts is None else max_verts
-        max_faces = counts[1] if max_faces is None else max_faces
-    verts = torch.zeros(B, int(max_verts), 3, device=dev, dtype=torch.float32)
-    faces = torch.zeros(B, int(max_faces), 3, device=dev, dtype=torch.int32)
-    run(verts, faces, int(max_verts), int(max_faces))
-    return verts, faces, nv, nf
-
-
-@torch.no_grad()
-def eval_surface(pred_verts, pred_n_verts, gt_verts, gt_faces, gt_n_faces=None, n_samples: int = 2048, seed: int = 0,
-                 extras: bool = False):
-    """hoisdf_eval_surface: predicted vertices (B, max_verts, 3) with counts (B,) against the ground-truth mesh gt_verts (B, V, 3),
-    gt_faces (F, 3) shared or (B, F, 3) with counts gt_n_faces -> a dict of (B,) tensors: pred_to_gt, gt_to_pred, chamfer (mean
-    squared distances, square metres) and n_used int32 (0: the sample has no predicted vertex or no usable face, and zeros).
-    With extras also samples (B, n_samples, 3), the points drawn on the ground-truth surface, and nearest (B, n_samples) int32."""
-    pred_verts = pred_verts.contiguous().float()
-    _chk(pred_verts)
-    if pred_verts.dim() != 3 or pred_verts.shape[2] != 3:
-        raise ValueError(f"eval_surface: predicted {tuple(pred_verts.shape)}: (B, max_verts, 3)")
-    dev, B, mv = pred_verts.device, pred_verts.shape[0], pred_verts.shape[1]
-    m = _Mesh(gt_verts, gt_faces, gt_n_faces, B, "eval_surface: ground-truth")
-    pn = _counts(pred_n_verts, B, dev, "eval_surface: pred_n_verts")
-    ws, nws = _workspace("hoisdf_eval_surface_workspace_bytes", B, mv, m.F, int(n_samples), dev)
-    out ={"pred_to_gt": torch.empty(B, device=dev, dtype=torch.float32), "gt_to_pred": torch.empty(B, device=dev, dtype=torch.float32),
-           "chamfer": torch.empty(B, device=dev, dtype=torch.float32), "n_used": torch.empty(B, device=dev, dtype=torch.int32)}
-    samples = torch.empty(B, int(n_samples), 3, device=dev, dtype=torch.float32) if extras else None
-    nearest = torch.empty(B, int(n_samples), device=dev, dtype=torch.int32) if extras else None
-    call("hoisdf_eval_surface", _p(pred_verts), _p(pn), mv, C.addressof(m.desc), B, int(n_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
-         _p(out["pred_to_gt"]), _p(out["gt_to_pred"]), _p(out["chamfer"]), _p(out["n_used"]), _p(samples), _p(nearest), _p(ws), nws, _st())
-    if extras:
-        out["samples"], out["nearest"] = samples, nearest
-    return out
-
-
-# ---------------------------------------------------------------------------------------------
-# Mesh rasteriser (csrc/raster.hip: hoisdf_raster_meshes, hoisdf_raster_overlay, hoisdf_eval_silhouette).  No gradient.
-# ---------------------------------------------------------------------------------------------
-@torch.no_grad()
-def raster_meshes(hand_verts, hand_faces, obj_verts, obj_faces, K, width: int, height: int, hand_n_faces=None, obj_n_faces=None,
-                  half_pixel: bool = False, near: float = 0.01, hm_shape=None, want=("ids", "depth", "counts"), out=None):
-    """hoisdf_raster_meshes: the hand mesh (B, Vh, 3) and the object mesh (B, Vo, 3), one camera frame, metres, faces (F, 3) shared
-    or (B, F, 3) with counts (B,), either mesh None; K (B, 6) or (B, 2, 3) = the top two rows of the camera matrix -> a dict with
-    what `want` names: ids int32 (B, height, width) (-1: background, else mesh << 16 | face row), depth float32 (0: background),
-    counts int32 (B, 2) = visible pixels per mesh and, with hm_shape = (hm_h, hm_w), hand_seg / obj_seg float32 (B, hm_h, hm_w):
-    the modal masks under the NEAREST fold of image_crop.  `out`: a dict of tensors to write into instead of new ones."""
-    if hand_verts is None and obj_verts is None:
-        raise ValueError("raster_meshes: one mesh at least")
-    mh = None if hand_verts is None else _Mesh(hand_verts, hand_faces, hand_n_faces, None, "raster_meshes: hand")
-    mo = None if obj_verts is None else _Mesh(obj_verts, obj_faces, obj_n_faces, mh and mh.B, "raster_meshes: object")
-    dev, B = (mh or mo).verts.device, (mh or mo).B
-    K = K.to(dev).float().reshape(B, 6).contiguous()
-    _chk(K)
-    names = list(want) + (["hand_seg", "obj_seg"] if hm_shape is not None else [])
-    shapes = {"ids": ((B, int(height), int(width)), torch.int32), "depth": ((B, int(height), int(width)), torch.float32),
-              "counts": ((B, 2), torch.int32)}
-    if hm_shape is not None:
-        shapes["hand_seg"] = shapes["obj_seg"] = ((B, int(hm_shape[0]), int(hm_shape[1])), torch.float32)
-    res = {}
-    for k in names:
-        shape, dtype = shapes[k]
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"raster_meshes: out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        res[k] = t
-    ws, nws = _workspace("hoisdf_raster_workspace_bytes", B, mh.F if mh else 0, mo.F if mo else 0, dev)
-    hm_h, hm_w = (int(hm_shape[0]), int(hm_shape[1])) if hm_shape is not None else (0, 0)
-    call("hoisdf_raster_meshes", mh and C.addressof(mh.desc), mo and C.addressof(mo.desc), _p(K), B, int(width),
-         int(height), int(bool(half_pixel)), float(near), _p(res.get("ids")), _p(res.get("depth")), _p(res.get("hand_seg")),
-         _p(res.get("obj_seg")), hm_w, hm_h, _p(res.get("counts")), _p(ws), nws, _st())
-    return res
-
-
-@torch.no_grad()
-def raster_overlay(ids, image, colour=((70, 130, 255), (255, 160, 40)), alpha: int = 160, out=None):
-    """hoisdf_raster_overlay: ids int32 (B, H, W) of raster_meshes over image uint8 (B, H, W, 3) -> uint8 (B, H, W, 3): a covered pixel
-    is (alpha colour[mesh] + (256 - alpha) image + 128) >> 8 with colour = (hand rgb, object rgb), a background pixel is copied.
-    out may be `image` itself (in place)."""
-    ids = ids.contiguous()
-    image = image.contiguous()
-    if not ids.is_cuda or image.device != ids.device:
-        raise RuntimeError("hoisdf_amd ops need CUDA/HIP tensors on one device (no CPU fallback)")
-    if ids.dtype != torch.int32 or image.dtype != torch.uint8 or ids.dim() != 3 or tuple(image.shape) != tuple(ids.shape) + (3,):
-        raise ValueError(f"raster_overlay: ids int32 (B, H, W) {tuple(ids.shape)} and image uint8 (B, H, W, 3) {tuple(image.shape)}")
-    if out is None:
-        out = torch.empty_like(image)
-    elif out.shape != image.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != image.device:
-        raise ValueError("raster_overlay: out must be a contiguous uint8 tensor of the image's shape on its device")
-    col = (C.c_uint8 * 6)(*[int(c) for m in colour for c in m])
-    B, H, W = ids.shape
-    call("hoisdf_raster_overlay", _p(ids), _p(image), _p(out), C.addressof(col), int(alpha), B, W, H, _st())
-    return out
-
-
-@torch.no_grad()
-def eval_silhouette(pred_hand, pred_obj, gt_hand, gt_obj):
-    """hoisdf_eval_silhouette: four masks (B, ...) float32, set where > 0.5 -> int32 (B, 4): hand intersection, hand union, object
-    intersection, object union of predicted against ground truth (integer sums on the device)"""
-    B = pred_hand.shape[0]
-    masks = [m.reshape(B, -1).float().contiguous() for m in (pred_hand, pred_obj, gt_hand, gt_obj)]
-    _chk(*masks)
-    if any(m.shape != masks[0].shape for m in masks):
-        raise ValueError(f"eval_silhouette: four masks of one shape, got {[tuple(m.shape) for m in masks]}")
-    counts = torch.empty(B, 4, device=masks[0].device, dtype=torch.int32)
-    call("hoisdf_eval_silhouette", *[_p(m) for m in masks], B, masks[0].shape[1], _p(counts), _st())
-    return counts
-
-
-# ---------------------------------------------------------------------------------------------
-# Silhouette loss (csrc/silhouette_loss.hip: hoisdf_mask_edt, hoisdf_silhouette_loss_fwd / _bwd): a mask's exact distance transform,
-# and one projected point set held to a pair of mask maps, with the gradient to the points.
-# ---------------------------------------------------------------------------------------------
-def _mask_maps(what: str, *masks):
-    """float masks (B, h, w) of one shape (None stays None) -> contiguous float32 tensors, B, h, w"""
-    ms = [None if m is None else m.detach().float().contiguous() for m in masks]
-    _chk(*ms)
-    first = next(m for m in ms if m is not None)
-    if first.dim() != 3 or any(m is not None and m.shape != first.shape for m in ms):
-        raise ValueError(f"{what}: masks of one shape (B, h, w), got {[None if m is None else tuple(m.shape) for m in ms]}")
-    return ms, first.shape[0], first.shape[1], first.shape[2]
-
-
-@torch.no_grad()
-def mask_edt(mask, mask_or=None, want_nearest: bool = False):
-    """hoisdf_mask_edt: mask (B, h, w) float32, set where > 0.5 (with mask_or: the union of the two) -> d2 int32 (B, h, w): the exact
-    squared distance in pixels^2 to the nearest set pixel (0 at a set pixel, EDT_NONE = 2^30 in a sample without one); with
-    want_nearest also nearest int32 (B, h, w): the index y' w + x' of a nearest set pixel, the lowest on a tie (-1 without one)."""
-    if mask is None:
-        raise ValueError("mask_edt: a mask")
-    (mask, mask_or), B, h, w = _mask_maps("mask_edt", mask, mask_or)
-    d2 = torch.empty(B, h, w, device=mask.device, dtype=torch.int32)
-    nearest = torch.empty_like(d2) if want_nearest else None
-    call("hoisdf_mask_edt", _p(mask), _p(mask_or), B, w, h, _p(d2), _p(nearest), _st())
-    return (d2, nearest) if want_nearest else d2
-
-
-def silhouette_workspace_views(ws, B: int, V: int, h: int, w: int):
-    """the pieces of a hoisdf_silhouette_loss_fwd workspace (the layout include/hoisdf.h states: each piece rounded up to 256
-    bytes) as tensors over it -> dict: u, v float64 (B, V), cell int32 (B, V), nearest int32 (B, h, w), den float64 (B, 2)"""
-    up = lambda n: (n + 255) // 256 * 256
-    out, off = {}, 0
-    for name, dtype, shape in (("u", torch.float64, (B, V)), ("v", torch.float64, (B, V)), ("cell", torch.int32, (B, V)),
-                               ("nearest", torch.int32, (B, h, w)), ("den", torch.float64, (B, 2))):
-        n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-        out[name] = ws[off:off + n].view(dtype).view(shape)
-        off += up(n)
-    return out
-
-
-class _SilhouetteLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, K, allow_d2, cover, nv, weight, stride, near):
-        dev, (B, V, _) = verts.device, verts.shape
-        h, w = cover.shape[1:]
-        v = verts.detach().contiguous()
-        ws, nws = _workspace("hoisdf_silhouette_loss_workspace_bytes", B, V, w, h, dev)
-        inside, cov = torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32)
-        common = (_p(v), _p(nv), V, _p(K), B, _p(allow_d2), _p(cover), w, h, float(near), _p(weight), stride)
-        call("hoisdf_silhouette_loss_fwd", *common, _p(inside), _p(cov), _p(ws), nws, _st())
-        # the backward reads the workspace and every input again: they stay alive, and unchanged, with the context
-        ctx.keep = (v, nv, K, allow_d2, cover, weight, ws)
-        ctx.common, ctx.nws = common, nws
-        ctx.set_materialize_grads(False)
-        return inside, cov
-
-    @staticmethod
-    def backward(ctx, g_inside, g_cover):
-        gs = [None if g is None else g.contiguous().float() for g in (g_inside, g_cover)]
-        _chk(*gs)
-        d_verts = torch.empty_like(ctx.keep[0])
-        call("hoisdf_silhouette_loss_bwd", *ctx.common, _p(gs[0]), _p(gs[1]), _p(d_verts), _p(ctx.keep[-1]), ctx.nws, _st())
-        return d_verts, None, None, None, None, None, None, None
-
-
-def silhouette_loss(verts, K, allow_d2, cover, n_verts=None, weight=None, near: float = 0.01):
-    """hoisdf_silhouette_loss_fwd / _bwd: verts (B, V, 3) camera frame, metres; K (B, 6) or (B, 2, 3) FOR THE MASK GRID (mask pixel
-    (px, py) sits at (px, py): render.mask_camera_rows); allow_d2 int32 (B, h, w) of ``mask_edt``: where the projected vertices may
-    lie; cover float32 (B, h, w), set where > 0.5: the pixels that want a projected vertex near them; n_verts (B,) or None: rows
-    from there on are padding; weight (V,) or (B, V) or None = ones -> (inside, cover), each (B,), in mask pixels: the weighted mean
-    over the vertices of the bilinear read of sqrt(allow_d2) plus the distance back onto the map, and the mean over cover's set
-    pixels of the distance to the nearest projected vertex.  The gradient flows to verts only; order-fixed: two calls give the
-    same bits."""
-    if verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError(f"silhouette_loss: verts {tuple(verts.shape)} must be (B, V, 3)")
-    _chk(verts)
-    dev, (B, V, _) = verts.device, verts.shape
-    (cover,), Bm, h, w = _mask_maps("silhouette_loss", cover)
-    allow_d2 = allow_d2.contiguous()
-    if Bm != B or tuple(allow_d2.shape) != (B, h, w) or allow_d2.dtype != torch.int32 or allow_d2.device != dev or cover.device != dev:
-        raise ValueError(f"silhouette_loss: allow_d2 int32 and cover float32, both ({B}, h, w) on {dev}; got {tuple(allow_d2.shape)} "
-                         f"{allow_d2.dtype} and {tuple(cover.shape)}")
-    K = K.detach().to(dev).float().reshape(B, 6).contiguous()
-    nv = _counts(n_verts, B, dev, "silhouette_loss: n_verts")
-    if weight is not None:
-        weight = torch.as_tensor(weight).detach().to(dev, torch.float32).contiguous()
-        if weight.shape not in ((V,), (B, V)):
-            raise ValueError(f"silhouette_loss: weight {tuple(weight.shape)}: ({V},) or ({B}, {V})")
-    stride = 0 if weight is None or weight.dim() == 1 else V
-    return _SilhouetteLoss.apply(verts, K, allow_d2, cover, nv, weight, stride, float(near))

@@ -9,6 +9,7 @@ import torch
 
 from . import ops
 from ._lib import call
+from ._marshal import _p, _st
 
 CHUNK = 16384
 
@@ -82,7 +83,7 @@ class FusedAdamW(torch.optim.AdamW):
                     self._table[(gi, si)] = cached
                 for p in sub:
                     self.state[p]["step"] += 1
-                call("hoisdf_adamw_step", ops._p(cached[1]), cached[1].shape[0], float(group["lr"]), float(b1), float(b2),
-                     float(group["eps"]), float(group["weight_decay"]), int(step0 + 1.0), self.grad_scale, ops._st())
+                call("hoisdf_adamw_step", _p(cached[1]), cached[1].shape[0], float(group["lr"]), float(b1), float(b2),
+                     float(group["eps"]), float(group["weight_decay"]), int(step0 + 1.0), self.grad_scale, _st())
         ops.bump_weight_generation()         # parameters changed without bumping torch's version counters
         return loss

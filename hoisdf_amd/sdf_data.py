@@ -21,8 +21,7 @@ import torch
 
 from . import ops
 from ._lib import call
-
-_p, _st = ops._p, ops._st
+from ._marshal import _p, _st
 
 
 def load_frame(path: str) -> np.ndarray:
