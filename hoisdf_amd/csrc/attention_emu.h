@@ -56,4 +56,7 @@ __device__ __forceinline__ bool emu_block(int nx, int nbh, int& tile, int& bh) {
 int attention_bwd4_emu_launch(const emu_attn::EmuAttn& a, hipStream_t st);
 // attention_emu_bwd4h.hip: the f16x2 form (two f16 planes per operand in a.q / a.k / a.v / a.d, per-(sample, head) scales from a.q_hm / k_hm / v_hm / d_hm)
 int attention_bwd4h_emu_launch(const emu_attn::EmuAttn& a, hipStream_t st);
+// attention_emu_bwd4g.hip: the f16x2 form with two dS pieces; behind a.dq_scale's B H floats it reads the 2 B H bound words of
+// emu_attn_delta_bound_kernel (attention_emu.hip): [2 bh] = bits of max_q ||dO[q]||_2, [2 bh + 1] = bits of max_q |delta[q]|
+int attention_bwd4g_emu_launch(const emu_attn::EmuAttn& a, hipStream_t st);
 }  // namespace hoisdf

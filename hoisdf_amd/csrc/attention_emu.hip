@@ -14,13 +14,15 @@
 //               contribution goes to a per-key-block partial buffer [kb][bh][q][64]; a reduce pass (here) sums the key blocks in
 //               order: no atomics anywhere, run-to-run identical.
 // The dropout mask is the same function of (seed, query, key) as in the f32 kernels.
+#include <stdlib.h>
+
 #include "attention_emu.h"
 
 namespace hoisdf {
 using namespace emu_attn;
 
 namespace {
-constexpr int RP = 72;              // bf16 per row of a row-major [32][64] tile in LDS (144 B)
+constexpr int RP = 72;             // bf16 per row of a row-major [32][64] tile in LDS (144 B)
 constexpr int TPH = 36;             // bf16 per row of a transposed [64][32] tile in LDS (72 B: conflict-free 8-byte reads)
 constexpr int ROWS_T = 32 * RP;     // bf16 per row-major plane tile
 constexpr int TRN_T = 64 * TPH;     // bf16 per transposed plane tile
@@ -437,6 +439,46 @@ __global__ __launch_bounds__(256) void emu_attn_delta_kernel(const float* __rest
   if (l16 == 0) delta[((size_t)b * H + head) * Lq + q] = s;
 }
 
+// The same delta, and the two BOUND WORDS per (b, head) that the two-piece f16x2 backward (attention_emu_bwd4g.hip) takes its dS scale
+// from: bound[2 bh] = bits of max_q ||dO[q]||_2, bound[2 bh + 1] = bits of max_q |delta[q]| (zero on entry; non-negative floats order
+// like their bits, so the unsigned atomic max is order-independent: run-to-run identical).  The norm is taken of the row scaled by the
+// power of two of its own largest element (in [1, 2): 1e20-sized rows do not overflow, 1e-30-sized ones do not flush).  One block per
+// sample and 128 consecutive (q, head) pairs - the row reads stay the contiguous ones of the kernel above - folding in LDS first:
+// 2 H global atomics per block.
+__global__ __launch_bounds__(256) void emu_attn_delta_bound_kernel(const float* __restrict__ o, int ldo, const float* __restrict__ dout,
+                                                                   int lddo, float* __restrict__ delta, uint32_t* __restrict__ bound,
+                                                                   int B, int H, int Lq) {
+  extern __shared__ uint32_t bmax[];                        // [H][2]
+  for (int i = threadIdx.x; i < 2 * H; i += 256) bmax[i] = 0u;
+  __syncthreads();
+  const int per_b = (Lq * H + 127) / 128;
+  const int b = blockIdx.x / per_b, chunk = blockIdx.x - b * per_b;
+  const int l16 = threadIdx.x & 15;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int gl = chunk * 128 + r * 16 + (threadIdx.x >> 4);
+    if (gl >= Lq * H) break;
+    const int q = gl / H, head = gl - q * H;
+    const float4 x = *reinterpret_cast<const float4*>(o + ((size_t)b * Lq + q) * ldo + head * D + l16 * 4);
+    const float4 y = *reinterpret_cast<const float4*>(dout + ((size_t)b * Lq + q) * lddo + head * D + l16 * 4);
+    float s = x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
+    const uint32_t m = group_max_u32<16>(mag_bits4(y));
+    const uint32_t e = min(max(m >> 23, 1u), 253u);          // the row's power of two, clamped so that both factors are normal numbers
+    const float dn = __builtin_bit_cast(float, (254u - e) << 23), up = __builtin_bit_cast(float, e << 23);
+    const float y0 = y.x * dn, y1 = y.y * dn, y2 = y.z * dn, y3 = y.w * dn;
+    float n2 = y0 * y0 + y1 * y1 + y2 * y2 + y3 * y3;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) { s += __shfl_xor(s, off, 16); n2 += __shfl_xor(n2, off, 16); }
+    if (l16 == 0) {
+      delta[((size_t)b * H + head) * Lq + q] = s;
+      atomicMax(bmax + 2 * head, mag_bits(fminf(sqrtf(n2) * up, 0x1p127f)));
+      atomicMax(bmax + 2 * head + 1, mag_bits(fminf(fabsf(s), 0x1p127f)));
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * H; i += 256) atomicMax(bound + (size_t)2 * b * H + i, bmax[i]);
+}
+
 // dq[b][q][head * 64 + d] = 0.125 * sum_kb part[kb][bh][q][d] in key-block order (one float4 per thread)
 // scale: null = 0.125 (the bf16x3 backward: Q pre-scaled by log2(e) / 8 ...); the f16x2 backward leaves 0.125 / (sK sS) per (b, head) there
 __global__ __launch_bounds__(256) void emu_attn_dq_reduce_kernel(const float* __restrict__ part, int nkb, float* __restrict__ dq,
@@ -683,6 +725,18 @@ extern "C" int hoisdf_attention_bwd_emu_mag(const float* q, int ldq, const float
   return attention_bwd_emu_mag(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, dk, dv, B, H, Lq, Lk, kv_len, drop_p, seed,
                                fwd_workspace, workspace, workspace_bytes, g_mag, stream, q_mag, k_mag, v_mag, do_mag);
 }
+// The dS pieces of the f16x2 backward: 2 (default; emu_attn_bwd4g_kernel, 60 MFMAs per query tile, the dS scale follows the data) or 3
+// (HOISDF_ATTN_BWD_DS=3, read at first use, or hoisdf_set_attn_bwd_ds(3): emu_attn_bwd4h_kernel, 76 MFMAs, fixed dS scale).  Per call.
+namespace {
+int g_ds_pieces = -1;
+int attn_bwd_ds_pieces() {
+  if (g_ds_pieces < 0) { const char* e = getenv("HOISDF_ATTN_BWD_DS"); g_ds_pieces = (e && e[0] == '3') ? 3 : 2; }
+  return g_ds_pieces;
+}
+}  // namespace
+extern "C" void hoisdf_set_attn_bwd_ds(int pieces) { g_ds_pieces = pieces == 3 ? 3 : 2; }
+extern "C" int hoisdf_get_attn_bwd_ds(void) { return attn_bwd_ds_pieces(); }
+
 // (internal, common.h) + g_mag: ONE array of row magnitudes for dq, dk and dv together (rows b L + s of a [dq | dk | dv] matrix: Lq == Lk;
 // zero on entry; null = not wanted)
 int hoisdf::attention_bwd_emu_mag(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, int ldo,
@@ -720,16 +774,30 @@ int hoisdf::attention_bwd_emu_mag(const float* q, int ldq, const float* k, int l
   }
   if (int rc = convert(dout, lddo, Lq, (int)pad128(Lq), B, H, 1.f, pd, st, do_hm)) return rc;
   const long ng = (long)B * Lq * H;
-  hipLaunchKernelGGL(emu_attn_delta_kernel, dim3((unsigned)((ng * 16 + 255) / 256)), dim3(256), 0, st, o, ldo, dout, lddo, delta, B, H, Lq);
+  // the f16x2 form's per-(b, head) words live in the third dO plane, which that form does not use: B H floats for the reduce pass
+  // (dq_scale), then - two dS pieces - the 2 B H bound words of the delta pass
+  float* const head_words = reinterpret_cast<float*>(pd.r[2]);
+  const bool two_piece = h2 && attn_bwd_ds_pieces() == 2;
+  if (two_piece) {
+    uint32_t* const bound = reinterpret_cast<uint32_t*>(head_words + (size_t)B * H);
+    if (hipMemsetAsync(bound, 0, (size_t)2 * B * H * sizeof(uint32_t), st) != hipSuccess) {
+      set_error("attention_bwd_emu: cannot zero the bound words");
+      return HOISDF_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(emu_attn_delta_bound_kernel, dim3((unsigned)(B * cdiv(Lq * H, 128))), dim3(256), (size_t)2 * H * sizeof(uint32_t), st, o,
+                       ldo, dout, lddo, delta, bound, B, H, Lq);
+  } else {
+    hipLaunchKernelGGL(emu_attn_delta_kernel, dim3((unsigned)((ng * 16 + 255) / 256)), dim3(256), 0, st, o, ldo, dout, lddo, delta, B, H, Lq);
+  }
   if (int rc = check_launch("attention_emu_delta")) return rc;
   EmuAttn a = emu_args(B, H, Lq, Lk, kv_len, drop_p, seed);
   for (int i = 0; i < 3; ++i) { a.q[i] = s.q.r[i]; a.k[i] = s.k.r[i]; a.v[i] = s.v.r[i]; a.d[i] = pd.r[i]; }
   a.lse_in = lse; a.delta = delta; a.dq_part = part; a.dk = dk; a.dv = dv; a.ldk = ldk; a.ldv = ldv; a.mag = g_mag;
   if (h2) {
     a.q_hm = q_hm; a.k_hm = k_hm; a.v_hm = v_hm; a.d_hm = do_hm;
-    a.dq_scale = reinterpret_cast<float*>(pd.r[2]);          // (the third dO plane is free in this form: the reduce pass's B H factors live there)
+    a.dq_scale = head_words;
   }
-  if (int rc = h2 ? attention_bwd4h_emu_launch(a, st) : attention_bwd4_emu_launch(a, st)) return rc;
+  if (int rc = two_piece ? attention_bwd4g_emu_launch(a, st) : h2 ? attention_bwd4h_emu_launch(a, st) : attention_bwd4_emu_launch(a, st)) return rc;
   const long n4 = (long)B * H * Lq * 16;
   hipLaunchKernelGGL(emu_attn_dq_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, cdiv(kv_len, 128), dq, ldq,
                      B, H, Lq, g_mag, (const float*)(h2 ? a.dq_scale : nullptr));

@@ -24,30 +24,38 @@
 //       waves (8 query rows each, 256-byte rows to HBM).  Small products and x0 y0 in separate accumulators.
 //   dQ goes to a per-key-block partial buffer [kb][bh][q][64]; emu_attn_dq_reduce_kernel sums the key blocks in order.
 //
-// Two forms share this text.  A unit (attention_emu_bwd4.hip: bf16x3, attention_emu_bwd4h.hip: f16x2) defines, then includes this file:
-//   B4_NPL                        planes per operand of Q, K, V, dO (3 / 2); dS always has three
+// Three units share this text.  A unit (attention_emu_bwd4.hip: bf16x3, attention_emu_bwd4h.hip: f16x2, attention_emu_bwd4g.hip: f16x2
+// with two dS pieces) defines, then includes this file:
+//   B4_NPL                        planes per operand of Q, K, V, dO (3 / 2)
+//   [B4_DSPL]                     pieces of dS (default 3; attention_emu_bwd4g.hip: 2 - its dS scale follows the data)
 //   B4_MFMA                       the MFMA mnemonic; cvt2 / unpack2: f32 pair <-> one word of two 16-bit pieces
 //   B4_SCALES                     statements ahead of the resident loads that leave dk_scale / dv_scale (and whatever the units read)
 //   B4_FORM_STATE, B4_HB_PAIR     the form's registers of the main loop; what the hash base of an odd key adds
 //   HA HB HC [HD], B4_HASH_TILE0  the dropout decision units and their run for tile 0
-//   LQ DL PA PD [PE] QA           the arithmetic units that see the operand scales or the plane count
+//   LQ DL PA PD [PE] QA [QE]      the arithmetic units that see the operand scales or the plane count
 //   B4_PHASE_INC, B4_ITER         the generated schedule (tools/gen/attn_bwd4*_phase.py) and its macro
 //   B4_KERNEL, B4_LAUNCH, B4_WHO, B4_TAG   kernel, launcher, and the two spellings of the form in messages
 // Everything is macro text, not a template over the form: each kernel sees the tokens it saw when the text existed twice
 // (profiles/attn_emu_merge_codegen.txt).
 
+#ifndef B4_DSPL
+#define B4_DSPL 3
+#endif
+
 namespace hoisdf {
 namespace {
 constexpr int NPL = B4_NPL;
+constexpr int DSPL = B4_DSPL;
+static_assert(DSPL >= NPL && DSPL <= 3, "dS has at least the operands' pieces");
 constexpr int QD_PLANE = 32 * 64;            // bf16 per plane tile [32 q][64 d]
 constexpr int QD_BUF = 2 * NPL * QD_PLANE;   // one staging buffer: the Q planes, then the dO planes (24 / 16 KB)
 constexpr int TT_PLANE = 128 * 32;           // bf16 per dS^T plane [128 keys][32 q]
-constexpr int TT_BUF = 3 * TT_PLANE;         // 24 KB
+constexpr int TT_BUF = DSPL * TT_PLANE;      // 24 KB (16 KB with two dS pieces)
 constexpr int X_BUF = 2 * 32 * 64;           // floats per dQ exchange buffer [key half][32 q][64 d] (16 KB)
 constexpr int TT0 = 3 * QD_BUF;              // bf16 offset of the T^T buffers
 constexpr int X0_BYTES = (3 * QD_BUF + 2 * TT_BUF) * 2;
 constexpr int ST0_BYTES = X0_BYTES + 2 * X_BUF * 4;
-constexpr unsigned B4_LDS_BYTES = ST0_BYTES + 3 * 64 * 4;      // 156 416 B (bf16x3), 131 840 B (f16x2)
+constexpr unsigned B4_LDS_BYTES = ST0_BYTES + 3 * 64 * 4;      // 156 416 B (bf16x3), 131 840 B (f16x2), 115 456 B (f16x2, two dS pieces)
 
 // 16-byte chunk `ch` of row `r` of a [32][64] bf16 row tile.  The XOR (bits: r1, r2, r1 ^ r3) serves the three access patterns
 // without bank conflicts (brute-forced against the guide's lane groups): the 16-byte fragment reads of S / dP (16 lanes = rows
@@ -207,13 +215,14 @@ __global__ __launch_bounds__(256, 1) void B4_KERNEL(EmuAttn a) {
     f32x16 s, dp, dq;
     f32x4 xo0[2], xo1[2];
     bf16x8 fr[2][NPL];
-    u32x4 pwv[NPL][2], gwv[3][2];
+    u32x4 pwv[NPL][2], gwv[DSPL][2];
     f32x2 pe[8], pd[8], xx[8], ff[8];
     float dsc[16], lq[16], dl[16];
+    (void)ff;                                  // (the third dS piece's scratch: no unit of a two-piece dS names it)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dsc[r] = 1.f;
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
+    for (int p = 0; p < DSPL; ++p)
 #pragma unroll
       for (int i = 0; i < 2; ++i) { if (p < NPL) pwv[p][i] = u32x4{0u, 0u, 0u, 0u}; gwv[p][i] = u32x4{0u, 0u, 0u, 0u}; }
 
@@ -272,7 +281,7 @@ __global__ __launch_bounds__(256, 1) void B4_KERNEL(EmuAttn a) {
       PIN2(xx[m_]);                                                                                                    \
     }                                                                                                                  \
   } while (0)
-    // Q phase: dS = Pd dP - P delta (= P (dP dropout - delta); QA: the unit), three-way split -> gw; dS^T rows of the wave's keys -> T^T
+    // Q phase: dS = Pd dP - P delta (= P (dP dropout - delta); QA: the unit), DSPL-way split -> gw (QB QC QD: three pieces; QB and the unit's QE: two); dS^T rows of the wave's keys -> T^T
 #define QB(q_)                                                                                                         \
   do {                                                                                                                 \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                                 \
@@ -301,7 +310,7 @@ __global__ __launch_bounds__(256, 1) void B4_KERNEL(EmuAttn a) {
   } while (0)
 #define TW(g_)                                                                                                         \
   do {                                                                                                                 \
-    _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                                   \
+    _Pragma("unroll") for (int p_ = 0; p_ < DSPL; ++p_)                                                                 \
       *reinterpret_cast<u32x2*>(lds + tt_w + p_ * TT_PLANE + (tw0 ^ (8 * (g_)))) =                                      \
           u32x2{gwv[p_][(g_) >> 1][2 * ((g_) & 1)], gwv[p_][(g_) >> 1][2 * ((g_) & 1) + 1]};                            \
   } while (0)

@@ -936,8 +936,8 @@ _ATTENTION_EMU = os.environ.get("HOISDF_ATTENTION", "emu") != "f32"
 def set_attention_emu(on: bool) -> None:
     """cfg.attention_emu (default on; HOISDF_ATTENTION=f32 turns it off): the large attention calls (forward with dropout + LSE,
     fused one-pass backward) as fp32 emulated on the 16-bit MFMA pipes, f32 accumulation / softmax (csrc/attention_emu*).  Two
-    forms: f16x2 (default where the linear layers run it, _attn_h2: two scaled f16 pieces per operand, three products per product,
-    five where dS is an operand) and bf16x3 (HOISDF_ATTN_FORM=b3 / HOISDF_EMU_FORM=b3: exact three-way bf16 splits of Q, K, V, dO, P
+    forms: f16x2 (default where the linear layers run it, _attn_h2: two scaled f16 pieces per operand, three products per product -
+    dS too since its scale follows the data; HOISDF_ATTN_BWD_DS=3 keeps the three-piece dS with five) and bf16x3 (HOISDF_ATTN_FORM=b3 / HOISDF_EMU_FORM=b3: exact three-way bf16 splits of Q, K, V, dO, P
     and dS, six products per product).  fp32-equivalent results, no atomics.  Off: the exact-f32 MFMA kernels of csrc/attention.hip."""
     global _ATTENTION_EMU
     _ATTENTION_EMU = bool(on)
@@ -1018,7 +1018,7 @@ _ATTN_BWD_EMU = os.environ.get("HOISDF_ATTN_BWD", "emu") != "f32"
 def _emu_bwd() -> bool:
     """Emulated attention calls run their backward emulated as well (default; HOISDF_ATTN_BWD=f32 keeps the exact-f32 fused
     backward next to the emulated forward): the one-pass kernel of csrc/attention_emu_bwd4.inc in its two forms, attention_emu_bwd4.hip
-    (bf16x3) / attention_emu_bwd4h.hip (f16x2) - four waves of 32 keys, one wave per SIMD, dQ through per-key-block partials and an ordered reduce pass.  They are
+    (bf16x3) / attention_emu_bwd4g.hip (f16x2; attention_emu_bwd4h.hip with three dS pieces) - four waves of 32 keys, one wave per SIMD, dQ through per-key-block partials and an ordered reduce pass.  They are
     order-fixed (no atomics), so they are also what deterministic mode uses."""
     return _ATTN_BWD_EMU or deterministic()
 

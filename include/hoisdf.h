@@ -465,9 +465,15 @@ int hoisdf_attention_bwd_emu(const float* q, int ldq, const float* k, int ldk, c
                              const float* dout, int lddo, const float* lse, float* delta, float* dq, float* dk, float* dv, int B,
                              int H, int Lq, int Lk, int kv_len, float drop_p, uint64_t seed, const void* fwd_workspace,
                              void* workspace, long workspace_bytes, void* stream);
-/* the backward in the f16x2 form (emu_attn_bwd4h_kernel, round 5): Q, K, V, dO and P as two scaled f16 pieces (three products per
- * product), dS as three (its magnitude follows P: five products in dQ and dK) - 76 instead of 120 MFMAs per query tile; one pass, no
- * atomics, run-to-run identical like hoisdf_attention_bwd_emu.  q_mag / k_mag / v_mag: as hoisdf_attention_fwd_emu_mag; do_mag: the
+/* the backward in the f16x2 form: Q, K, V, dO, P and dS as two scaled f16 pieces each (three products per product in all five
+ * contractions, 60 instead of 120 MFMAs per query tile; emu_attn_bwd4g_kernel).  dS = Pd dP - P delta is scaled per (sample, head) by
+ * the largest power of two sS with sS Bd (1 + 2^-10) < 2^14, where
+ *     |dS_ij| <= Bd = inv_keep max_i ||dO_i||_2 8 max|V| + max_i |delta_i|
+ * (Cauchy-Schwarz on dP_ij = dO_i . v_j over d = 64; the two maxima are by-products of the delta pass, max|V| is the head magnitude):
+ * its two pieces carry the 22 bits of the other operands.  hoisdf_set_attn_bwd_ds(3) (environment HOISDF_ATTN_BWD_DS=3, read at first
+ * use) brings back the earlier kernel for the calls that follow: a fixed dS scale from |dP| <= 64 max|dO| max|V|, which flat softmaxes
+ * undershoot by ~20 binades, hence dS as THREE pieces (five products in dQ and dK, 76 MFMAs per query tile; emu_attn_bwd4h_kernel).
+ * Either way one pass, no atomics, run-to-run identical like hoisdf_attention_bwd_emu.  q_mag / k_mag / v_mag: as hoisdf_attention_fwd_emu_mag; do_mag: the
  * head magnitudes of dout (all required; hoisdf_head_mag_measure, or hoisdf_linear_bwd_input_emu_heads).  fwd_workspace: the planes a
  * forward OF THIS FORM kept, or NULL.  g_mag (optional, zero-filled, B L words; needs Lq == Lk): the row magnitudes of a [dq | dk | dv] matrix. */
 int hoisdf_attention_bwd_emu_mag(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, int ldo,
@@ -475,6 +481,9 @@ int hoisdf_attention_bwd_emu_mag(const float* q, int ldq, const float* k, int ld
                                  int H, int Lq, int Lk, int kv_len, float drop_p, uint64_t seed, const void* fwd_workspace,
                                  void* workspace, long workspace_bytes, const uint32_t* q_mag, const uint32_t* k_mag,
                                  const uint32_t* v_mag, const uint32_t* do_mag, uint32_t* g_mag, void* stream);
+/* the dS pieces of hoisdf_attention_bwd_emu_mag and of the layers that run it: 2 (default) or 3; process-wide, takes effect per call */
+void hoisdf_set_attn_bwd_ds(int pieces);
+int hoisdf_get_attn_bwd_ds(void);
 /* Small masked attention (17 MANO queries, tgt_mask of common/utils/misc.py:11-31):
  * mask [Lq][Lk] uint8, 1 = masked; Lq, Lk <= 64. probs [B][H][Lq][Lk] saved for backward. */
 int hoisdf_attention_small_fwd(const float* q, int ldq, const float* k, int ldk, const float* v,

@@ -10,7 +10,8 @@ CASES = {
     "attn_bwd_emu_32x2048x2048": ("hoisdf_attention_bwd_emu", "emu_attn_bwd4_kernel", (32, 2048, 2048)),
     # the f16x2 form of the encoder attention (default in the layers)
     "attn_fwd_h2_32x2048x2048": ("hoisdf_attention_fwd_emu_mag", "emu_attn_fwd2_kernel<true, 2, true>", (32, 2048, 2048)),
-    "attn_bwd_h2_32x2048x2048": ("hoisdf_attention_bwd_emu_mag", "emu_attn_bwd4h_kernel", (32, 2048, 2048)),
+    # (two dS pieces, the default; HOISDF_ATTN_BWD_DS=3 runs emu_attn_bwd4h_kernel)
+    "attn_bwd_h2_32x2048x2048": ("hoisdf_attention_bwd_emu_mag", "emu_attn_bwd4", (32, 2048, 2048)),
     "attn_fwd_bf16x2_4x8192x8192": ("hoisdf_attention_fwd_bf16x2", "emu_attn_fwd2_kernel<false, 2>", (4, 8192, 8192)),
     # the f16x2 form of the linear layers (default; what the Python path calls: the *_mag entries after one hoisdf_mag_measure per operand)
     "linear_fwd_emu_65536x1024x256": ("hoisdf_linear_fwd_emu_mag", "emu_h2_kernel<false, false, 2>", (65536, 1024, 256)),
