@@ -103,6 +103,16 @@ class Config:
     field_grid = 64                      # nodes per axis of the fine grid (the coarse one has half as many)
     field_max_verts = 131072             # vertex rows per sample of the fixed-capacity outputs; twice as many face rows
     field_samples = 4096                 # points drawn on the ground-truth surface for the gt -> prediction half
+    # not in the reference: the eval forward moves the predicted hand mesh and the predicted object, each as a rigid body, onto the
+    # zero level set of the field the same network predicts (refine.fit_pair: Model.field_values + hoisdf_field_fit,
+    # csrc/field_fit.hip) and adds refined_{hand,obj}_verts / refine_{hand,obj}_{rot,trans,cost,info} to its outputs; the Evaluator
+    # appends a Refined: block to results.txt.  Also HOISDF_REFINE=1 / Evaluator(refine=True) / test.py --refine.  Needs
+    # Model.set_refine_source and meta_info["obj_cls"]; not offered on the one-call path (native_infer) or for the IK variant
+    eval_refine = False
+    refine_grid = None                   # nodes per axis of the field the fit reads; None: field_grid
+    refine_pad_cells = 4                 # coarse cells around the inside nodes: a fit starts OFF the surface
+    refine_iters = 32                    # tried steps at the most (<= HOISDF_FIELD_FIT_MAX_ITERS)
+    refine_huber = 0.1                   # field units: the residual beyond which the cost is linear (the field is tanh-shaped)
     # not in the reference: the mesh rasteriser (hoisdf_raster_meshes, csrc/raster.hip; hoisdf_amd/render.py), three uses, all off:
     #   seg_source = "mesh" (also HOISDF_SEG=mesh / Trainer(seg_source=...)): the trainer renders targets["hand_seg"] / ["obj_seg"] each
     #     step from the step's own label meshes through meta["cam_intr"] - the modal silhouettes, mutual occlusion included - instead

@@ -3,8 +3,10 @@
 The model learns two signed-distance fields (hand, object); Model.field_surface(return_values=True) gives them on a per-sample grid.
 Fitting the predicted mesh to the field the same network predicts is the test-time step of the SDF line this code descends from
 (Grasping Field, AlignSDF, gSDF): a small non-linear least-squares problem per sample.  This module fixes the rules of that fit and
-is their yardstick (tests/test_field_fit_oracle.py); it is NOT on the model's path and no fallback - the project's hot paths are HIP,
-and the one-launch kernel for these rules (one workgroup per sample, the summation order below) is not in the tree yet.
+is their yardstick (tests/test_field_fit_oracle.py); it is NOT on the model's path and no fallback - the project's hot paths are HIP:
+hoisdf_field_fit (csrc/field_fit.hip, csrc/field_fit_rules.h; ops.field_fit, refine.fit_pair) runs these rules with one workgroup
+per sample in the summation order below, as iters + 2 launches - the iteration over steps is the host's - and is held to this module
+(tests/test_field_fit_rules_host.py on the CPU, tests/test_gpu_field_fit.py on the GPU).
 Limits: the field is the trilinear interpolant of the grid values, not the network; rigid only, no articulation; no gradient.
 
 All arithmetic is float64 on the float32 inputs, every operation rounded on its own (no product fused into a sum), in the order

@@ -26,6 +26,9 @@ AlignSDF and gSDF, through hoisdf_eval_surface (ops.eval_surface) - and appends 
 ``Evaluator(silhouette=True)`` (``cfg.eval_silhouette`` / ``HOISDF_SILHOUETTE=1`` / ``test.py --silhouette``) renders the predicted pair
 with mutual occlusion (hoisdf_raster_meshes, csrc/raster.hip) and appends a ``Silhouette:`` block - the IoU of its two modal masks against
 the mask targets - after everything else.  Off by default.
+``Evaluator(refine=True)`` (``cfg.eval_refine`` / ``HOISDF_REFINE=1`` / ``test.py --refine``) measures the predicted pair before and after
+its rigid fit to the two learned fields (refine.fit_pair: hoisdf_field_fit, csrc/field_fit.hip, run by the eval forward) against the
+ground-truth meshes and appends a ``Refined:`` block after everything else.  Off by default.
 """
 from __future__ import annotations
 
@@ -292,26 +295,40 @@ class Evaluator:
     union against them on the device (ops.eval_silhouette); ``write`` reads the integer counts once, divides in float64 on the host
     and appends one ``Silhouette:`` block after everything else: the mean IoU of the hand and of the object over the samples that
     took part and the share of samples left out - an empty union, or obj_cls < 0.  It needs the same ``template_faces`` /
-    ``hand_faces``."""
+    ``hand_faces``.
+    ``refine=True`` (or cfg.eval_refine / HOISDF_REFINE=1; either backend; in the signature it stands before ``field``, which stays
+    last: pass the switches by keyword): where a batch carries the ground-truth MANO mesh and the refined pair of the eval forward
+    (``refined_{hand,obj}_verts``, ``refine_{hand,obj}_{cost,info}``: refine.fit_pair, hoisdf_field_fit), every ``feed`` measures the
+    mean vertex error of the hand against the ground-truth MANO mesh + mano_root and of the object against the template posed by the
+    ground-truth pose, before and after the fit, keeps running sums on the device, and ``write`` appends one ``Refined:`` block
+    after everything else: both errors in cm, the mean start and end cost and the mean tried steps per field over the samples that
+    took part, and the share left out - a fit without a point on the grid (info[0] == 0), for the object also obj_cls < 0.  It
+    needs the same ``template_faces`` / ``hand_faces`` (render.predicted_pair poses the pair from them)."""
 
     def __init__(self, cfg, templates: torch.Tensor, native: bool = False, interaction: bool = False,
                  template_faces: Optional[Dict[str, torch.Tensor]] = None, hand_faces: Optional[torch.Tensor] = None,
-                 silhouette: bool = False, field: bool = False):
+                 silhouette: bool = False, refine: bool = False, field: bool = False):
+        from .refine import enabled as refine_enabled
         self.cfg, self.templates, self.native = cfg, templates, bool(native)
         self.dev = templates.device
         self.interaction = bool(interaction) or interaction_enabled(cfg)
         self.field = bool(field) or field_enabled(cfg)
         self.silhouette = bool(silhouette) or silhouette_enabled(cfg)
+        self.refine = bool(refine) or refine_enabled(cfg)
         self._hfaces = None
+        if self.refine:
+            # per field (hand, obj): the sums of the mean vertex error before and after [m], of the start and the end cost and of the
+            # tried steps over the samples that took part, their number, the samples seen
+            self._racc = torch.zeros(2, 7, device=self.dev, dtype=torch.float64)
         if self.silhouette:
             self._scounts = []          # per feed: int32 (B, 5) on the device = the four counts of ops.eval_silhouette, obj_cls >= 0
         if self.field:
             # per field (hand, obj): the sum of the Chamfer distances [m^2] over the samples that took part, their number, the samples seen
             self._facc = torch.zeros(2, 3, device=self.dev, dtype=torch.float64)
         have_faces = template_faces is not None and hand_faces is not None and "faces" in template_faces
-        if (self.interaction or self.field or self.silhouette) and not have_faces:
-            raise ValueError("Evaluator(interaction=True) / Evaluator(field=True) / Evaluator(silhouette=True) needs template_faces "
-                             "(faces, n_faces of sdf_data.pack_templates) and hand_faces")
+        if (self.interaction or self.field or self.silhouette or self.refine) and not have_faces:
+            raise ValueError("Evaluator(interaction=True) / Evaluator(field=True) / Evaluator(silhouette=True) / Evaluator(refine=True) needs "
+                             "template_faces (faces, n_faces of sdf_data.pack_templates) and hand_faces")
         if have_faces:                                            # (also without a block: render.predicted_pair poses from them)
             self._tfaces = torch.as_tensor(template_faces["faces"]).to(self.dev, torch.int32)
             n = template_faces.get("n_faces")
@@ -389,6 +406,8 @@ class Evaluator:
         self._add({"ADDS_error": om["ADDS"], "mano_mje": mje, "mano_pamje": pamje, "OCE_error": om["OCE"], "MCE_error": om["MCE"]}, B, used)
         if self.field and cfg.eval_mesh and "mano_mesh_gt_out" in out and "field_hand_verts" in out:
             self._feed_field(out, tg, meta, obj_cls)
+        if self.refine and "mano_mesh_gt_out" in out and "refined_hand_verts" in out:
+            self._feed_refine(out, tg, meta, obj_cls)
         if cfg.eval_mesh and "mano_mesh_out" in out:
             pv, gv = out["mano_mesh_out"], out["mano_mesh_gt_out"]
             if self.native:
@@ -462,6 +481,36 @@ class Evaluator:
                                                 torch.tensor(float(used.numel()), device=self.dev, dtype=torch.float64)])
                                    for r, used in (res["hand"], res["obj"])])
 
+    def refine_per_sample(self, out, targets, meta, obj_cls):
+        """the refined pair of the eval forward (refine.fit_pair) against the ground truth -> {"hand": (before (B,), after (B,): the
+        mean vertex error in metres against the ground-truth MANO mesh + mano_root, cost (B, 2), info (B, 4), used (B,) bool),
+        "obj": the same against the template posed by the ground-truth rotation and translation + obj_center_cam}; used: the fit had
+        a point to work with (info[0] > 0), for the object also obj_cls >= 0"""
+        from .render import predicted_pair
+        dev = self.dev
+        root = meta["mano_root"].to(dev)
+        hand, _, obj, _, _, known = predicted_pair(out, meta, obj_cls, self)
+        cls = torch.as_tensor(obj_cls).to(dev).long().clamp_min(0)
+        gt_hand = out["mano_mesh_gt_out"].detach() + root[:, None]
+        R = batch_rodrigues(targets["obj_rot"].to(dev).reshape(-1, 3))
+        gt_obj = self.templates[cls] @ R.transpose(1, 2) + (targets["rel_obj_trans"].to(dev).reshape(-1, 3) + meta["obj_center_cam"].to(dev))[:, None]
+        res = {}
+        for kind, before, gt, ok in (("hand", hand, gt_hand, torch.ones_like(known)), ("obj", obj, gt_obj, known)):
+            after, info = out[f"refined_{kind}_verts"].to(dev), out[f"refine_{kind}_info"].to(dev)
+            err = lambda v: (v.double() - gt.double()).norm(dim=2).mean(1)
+            res[kind] = (err(before), err(after), out[f"refine_{kind}_cost"].to(dev), info, ok & (info[:, 0] > 0))
+        return res
+
+    def _feed_refine(self, out, targets, meta, obj_cls) -> None:
+        res = self.refine_per_sample(out, targets, meta, obj_cls)
+        rows = []
+        for before, after, cost, info, used in (res["hand"], res["obj"]):
+            u = used.double()
+            rows.append(torch.stack([(before * u).sum(), (after * u).sum(), (cost[:, 0] * u).sum(), (cost[:, 1] * u).sum(),
+                                     (info[:, 2].double() * u).sum(), u.sum(),
+                                     torch.tensor(float(used.numel()), device=self.dev, dtype=torch.float64)]))
+        self._racc += torch.stack(rows)
+
     def write(self, out_dir: str) -> str:
         """results.txt (and, for ho3d, pred_mano.json) under out_dir -> the path of results.txt"""
         os.makedirs(out_dir, exist_ok=True)
@@ -505,6 +554,14 @@ class Evaluator:
                 print("Silhouette:", file=f)
                 print("hand_iou=%.6f, obj_iou=%.6f, hand_left_out=%.3f, obj_left_out=%.3f"
                       % (line[0][1], line[1][1], line[0][2], line[1][2]), file=f)
+        if self.refine:                                        # after everything else
+            with open(path, "a") as f:
+                print("Refined:", file=f)
+                for name, (eb, ea, c0, c1, tried, n, seen) in zip(("hand", "obj"), self._racc.tolist()):
+                    d = max(n, 1.0)
+                    print("%s_vertex_error=%.4f cm -> %.4f cm, %s_cost=%.6f -> %.6f, %s_steps=%.2f, %s_left_out=%.3f"
+                          % (name, eb / d * 100.0, ea / d * 100.0, name, c0 / d, c1 / d, name, tried / d, name, 1.0 - n / max(seen, 1.0)),
+                          file=f)
         if self.ho3d:
             if self.native:
                 joints = list(torch.cat(self.joint_list).cpu().numpy()) if self.joint_list else []

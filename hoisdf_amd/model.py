@@ -390,9 +390,23 @@ class Model(nn.Module):
         -> (verts (B, max_verts, 3), faces (B, max_faces, 3) int32, n_verts (B,), n_faces (B,) int32: the counts needed) as
         ops.iso_surface returns them: with both capacities given nothing synchronises.  With ``return_values`` a fifth element,
         a dict: values (B, n^3), grid (B, 8), coarse_values (B, coarse_n^3), coarse_grid (B, 8), all in the scaled frame."""
-        c = self.cfg
         if kind not in ("hand", "obj"):
             raise ValueError(f"field_surface: kind={kind!r} ('hand' or 'obj')")
+        fv = self.field_values(feature_pyramid, meta_info, kind, n, coarse_n, box, chunk_rows=chunk_rows, pad_cells=pad_cells)
+        res = ops.iso_surface(fv["values"], fv["grid"], n, 0.0, max_verts, max_faces, out_scale=1.0 / fv["scale"], out_shift=fv["centre"])
+        if return_values:
+            return res + ({k: fv[k] for k in ("values", "grid", "coarse_values", "coarse_grid")},)
+        return res
+
+    @torch.no_grad()
+    def field_values(self, feature_pyramid, meta_info, kind="hand", n=64, coarse_n=32, box=None, *, chunk_rows=None, pad_cells=1):
+        """The learned hand / object field sampled on its refined grid: the part of ``field_surface`` before the extraction, for
+        whoever needs the values themselves (refine.fit_pair).  The grids, the chunking and the dropout rule are field_surface's.
+        -> a dict: values (B, n^3), grid (B, 8), coarse_values (B, coarse_n^3), coarse_grid (B, 8), all in the scaled frame
+        x_scaled = (x_cam - centre) * scale, and that frame's centre (B, 3) and scale (a float)."""
+        c = self.cfg
+        if kind not in ("hand", "obj"):
+            raise ValueError(f"field_values: kind={kind!r} ('hand' or 'obj')")
         pyr = self._pyramid(feature_pyramid)
         center = (meta_info["mano_root"] if kind == "hand" else meta_info["obj_center_cam"]).reshape(-1, 3).contiguous().float()
         scale = c.hand_sdf_scale if kind == "hand" else c.obj_sdf_scale
@@ -417,10 +431,7 @@ class Model(nn.Module):
         coarse = field(coarse_grid, coarse_n)
         grid = ops.iso_refine_grid(coarse, coarse_grid, coarse_n, 0.0, int(pad_cells), n)
         values = field(grid, n)
-        res = ops.iso_surface(values, grid, n, 0.0, max_verts, max_faces, out_scale=1.0 / scale, out_shift=center)
-        if return_values:
-            return res + ({"values": values, "grid": grid, "coarse_values": coarse, "coarse_grid": coarse_grid},)
-        return res
+        return {"values": values, "grid": grid, "coarse_values": coarse, "coarse_grid": coarse_grid, "centre": center, "scale": float(scale)}
 
     def field_enabled(self) -> bool:
         """cfg.eval_field (default False) or HOISDF_FIELD=1: the eval forward adds the two field surfaces to its outputs"""
@@ -436,6 +447,34 @@ class Model(nn.Module):
             v, f, nv, nf = self.field_surface(feature_pyramid, meta_info, kind, int(c.field_grid), max(int(c.field_grid) // 2, 2),
                                               max_verts=mv, max_faces=2 * mv)
             out.update({f"field_{kind}_verts": v, f"field_{kind}_faces": f, f"field_{kind}_n_verts": nv, f"field_{kind}_n_faces": nf})
+
+    def refine_enabled(self) -> bool:
+        """cfg.eval_refine (default False) or HOISDF_REFINE=1: the eval forward fits the predicted pair to the two learned fields"""
+        from .refine import enabled
+        return enabled(self.cfg)
+
+    def set_refine_source(self, source):
+        """what the refinement of the eval forward poses the predicted pair from: a render.PairSource (the templates as meshes and
+        the hand's faces; render.predicted_pair takes it).  A plain attribute, no submodule: the checkpoint schema stays as it is"""
+        object.__setattr__(self, "_refine_source", source)
+
+    def _refine_outputs(self, out, feature_pyramid, meta_info):
+        """the opt-in outputs of the eval forward: refined_{hand,obj}_verts (camera metres) and refine_{hand,obj}_{rot,trans,cost,
+        info} of refine.fit_pair on the predicted pair.  Needs ``set_refine_source`` and meta_info["obj_cls"].  Nothing synchronises."""
+        from .refine import fit_pair
+        from .render import predicted_pair
+        if getattr(self, "_refine_source", None) is None:
+            raise RuntimeError("cfg.eval_refine needs the templates: Model.set_refine_source(render.PairSource(cfg, templates, template_faces, hand_faces))")
+        if "obj_cls" not in meta_info:
+            raise KeyError("cfg.eval_refine needs meta_info['obj_cls']: the object template of every sample (-1: none)")
+        if self.cfg.use_inverse_kinematics:
+            raise ValueError("cfg.eval_refine needs the predicted hand mesh in the forward: the IK variant has none there")
+        pair = predicted_pair(out, meta_info, meta_info["obj_cls"], self._refine_source)
+        res = fit_pair(self, feature_pyramid, meta_info, pair)
+        out["refined_hand_verts"], out["refined_obj_verts"] = res["pair"][0], res["pair"][2]
+        for kind in ("hand", "obj"):
+            for k in ("rot", "trans", "cost", "info"):
+                out[f"refine_{kind}_{k}"] = res[kind][k]
 
     def render_gaussian_heatmap(self, joint_coord):
         """reference :128-143 (encoder-side auxiliary target; plain torch)."""
@@ -822,6 +861,8 @@ class Model(nn.Module):
         """eval forward with the switch on: the encoder in PyTorch (or, with cfg.native_encoder, through hoisdf_encoder_infer), then
         infer_native; dexycb keeps its ground-truth MANO outputs"""
         c = self.cfg
+        if self.refine_enabled():
+            raise ValueError("cfg.eval_refine is not offered on the one-call path (cfg.native_infer): run the eval forward without it")
         self._set_arithmetic()
         with torch.no_grad():
             counts = self.infer_native_begin(meta_info, self.linear_sdfin.layers[0].weight.shape[1])
@@ -856,6 +897,8 @@ class Model(nn.Module):
         loss, out = self.hot_path(pyr, inputs, targets, meta_info, mode, epoch_cnt, batch_ratio, branch_a, infer_counts)
         if mode != "train" and not self.training and self.field_enabled():
             self._field_outputs(out, pyr, meta_info)
+        if mode != "train" and not self.training and self.refine_enabled():
+            self._refine_outputs(out, pyr, meta_info)
         if mode == "train" or c.dataset == "dexycb":                                   # :404-422 aux image losses
             self._aux_outputs(out, targets, decoder_out)
             # (f4) one HIP pass: Gaussian heat-map target + MSE + the two BCE maps

@@ -6,7 +6,7 @@ CPU tensor or a missing library raises.
 
 This module is the model's step: everything a training or evaluation step of Model.hot_path runs, and the process-wide state
 those calls read (dropout seeds, the zero arena, the emulation switches, the weight generation).  The stateless entries live by
-kernel family in ops_eval (evaluation metrics), ops_mesh (mesh SDF, interaction, iso-surface, rasteriser, silhouette) and
+kernel family in ops_eval (evaluation metrics), ops_mesh (mesh SDF, interaction, iso-surface, field fit, rasteriser, silhouette) and
 ops_infer (whole-model / encoder inference, convolutions, IK) on the shared helpers of _marshal, and are re-exported here: callers
 keep saying ``ops.NAME``.  The import graph is _lib <- _marshal <- ops_eval / ops_mesh / ops_infer <- ops.
 """
@@ -30,7 +30,7 @@ from .ops_eval import (_eval_workspace, eval_accum_finish, eval_accum_init, eval
 from .ops_infer import (CONV_ACT, ConvWeight, EncoderPrepared, PoseInferCounts, PosePrepared, _conv_ws, _nhwc_slice, conv2d_nhwc, conv_plan,
                         encoder_infer, encoder_tensor_table, ik_mano, maxpool2d_nhwc, pose_infer)
 from .ops_mesh import (PreparedMesh, _as_prepared, _InteractionLoss, _iso_grid, _iso_values, _loss_weight, _mask_maps, _Mesh,
-                       _SilhouetteLoss, eval_interaction, eval_silhouette, eval_surface, interaction_loss,
+                       _SilhouetteLoss, eval_interaction, eval_silhouette, eval_surface, field_fit, interaction_loss,
                        iso_grid_points, iso_refine_grid, iso_surface, mask_edt, mesh_sample_points, mesh_sdf, mesh_sdf_rows,
                        raster_meshes, raster_overlay, silhouette_loss, silhouette_workspace_views)
 

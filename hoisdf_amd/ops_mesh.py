@@ -1,4 +1,4 @@
-"""Mesh entries (csrc/mesh_sdf.hip, interact.hip, interact_loss.hip, isosurf.hip, raster.hip, silhouette_loss.hip).  Stateless:
+"""Mesh entries (csrc/mesh_sdf.hip, interact.hip, interact_loss.hip, isosurf.hip, field_fit.hip, raster.hip, silhouette_loss.hip).  Stateless:
 marshal, size, allocate, one C call (the two losses: one per direction)."""
 from __future__ import annotations
 
@@ -305,6 +305,50 @@ def iso_surface(values, grid, n: int, iso: float = 0.0, max_verts: Optional[int]
     faces = torch.zeros(B, int(max_faces), 3, device=dev, dtype=torch.int32)
     run(verts, faces, int(max_verts), int(max_faces))
     return verts, faces, nv, nf
+
+
+@torch.no_grad()
+def field_fit(values, grid, n: int, points, n_points=None, pivot=None, iters: int = 32, huber: float = 0.1, lambda0: float = 1e-3,
+              step_tol: float = 1e-7, min_used_percent: int = 50, want=()):
+    """hoisdf_field_fit: the points (B, V, 3), in the frame of the field ``values`` (B, n^3) on ``grid`` (B, 8), moved as a rigid
+    body onto the field's zero level set (include/hoisdf.h "field fit"; the rules: hoisdf_amd/field_fit_oracle.py).  n_points (B,)
+    or None: the rows of each sample that count (rows beyond are not read; their rows of points_out stay zero); pivot (B, 3) or
+    None = the mean of the sample's points.  iters + 2 launches, nothing synchronises; order-fixed: two calls give the same bits.
+    -> a dict of device tensors: rot (B, 3, 3), trans (B, 3), points_out (B, V, 3) float32; cost (B, 2) float64 = start, end;
+    info (B, 4) int32 = points taking part at the start, at the end, steps tried, steps accepted; and what ``want`` names of
+    normal (B, 56) float64 = the start pose's 28 sums and their magnitude sums, pose64 (B, 12) float64 = R, t unrounded."""
+    grid, B, N = _iso_grid(grid, n)
+    if values.dim() != 2 or values.shape != (B, N) or values.dtype != torch.float32 or values.stride(1) != 1 or \
+            (B > 1 and values.stride(0) < N):
+        values = values.reshape(B, N).float().contiguous()
+    points = points.contiguous().float()
+    _chk(values, points)
+    if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3:
+        raise ValueError(f"field_fit: points {tuple(points.shape)}: (V, 3) per sample of {B}")
+    unknown = set(want) - {"normal", "pose64"}
+    if unknown:
+        raise ValueError(f"field_fit: want names {sorted(unknown)}; 'normal' and 'pose64' exist")
+    dev, V = grid.device, points.shape[1]
+    ld = values.stride(0) if B > 1 else max(values.stride(0), N)
+    nv = _counts(n_points, B, dev, "field_fit: n_points")
+    if pivot is not None:
+        pivot = pivot.reshape(B, 3).contiguous().float()
+        _chk(pivot)
+    ws, nws = _workspace("hoisdf_field_fit_workspace_bytes", B, dev)
+    f64 = dict(device=dev, dtype=torch.float64)
+    out = {"rot": torch.empty(B, 3, 3, device=dev, dtype=torch.float32), "trans": torch.empty(B, 3, device=dev, dtype=torch.float32),
+           "points_out": torch.zeros(B, V, 3, device=dev, dtype=torch.float32), "cost": torch.empty(B, 2, **f64),
+           "info": torch.empty(B, 4, device=dev, dtype=torch.int32)}
+    normal = torch.empty(B, 56, **f64) if "normal" in want else None
+    pose64 = torch.empty(B, 12, **f64) if "pose64" in want else None
+    call("hoisdf_field_fit", _p(values), ld, _p(grid), int(n), _p(points), V, _p(nv), _p(pivot), B, int(iters), float(huber),
+         float(lambda0), float(step_tol), int(min_used_percent), _p(out["rot"]), _p(out["trans"]), _p(out["points_out"]),
+         _p(out["cost"]), _p(out["info"]), _p(normal), _p(pose64), _p(ws), nws, _st())
+    if normal is not None:
+        out["normal"] = normal
+    if pose64 is not None:
+        out["pose64"] = pose64
+    return out
 
 
 @torch.no_grad()

@@ -86,10 +86,27 @@ class MeshSegSource:
         targets["hand_seg"], targets["obj_seg"] = res["hand_seg"], res["obj_seg"]
 
 
+class PairSource:
+    """What ``predicted_pair`` needs to pose the pair, and nothing else: the object templates as meshes and the hand's faces on one
+    device.  templates (T, V, 3); template_faces = the ``faces`` (T, F, 3) / ``n_faces`` (T,) of sdf_data.pack_templates (whose
+    ``verts`` are ``templates``); hand_faces (Fh, 3) = the MANO layer's ``th_faces``.  For a caller without an Evaluator: the
+    refinement of the eval forward (Model.set_refine_source)."""
+
+    def __init__(self, cfg, templates: torch.Tensor, template_faces: Dict[str, torch.Tensor], hand_faces: torch.Tensor):
+        self.cfg, self.templates, self.dev = cfg, templates, templates.device
+        self._tfaces = torch.as_tensor(template_faces["faces"]).to(self.dev, torch.int32)
+        n = template_faces.get("n_faces")
+        self._tn = (torch.full((self._tfaces.shape[0],), self._tfaces.shape[1], dtype=torch.int32) if n is None else torch.as_tensor(n))
+        self._tn = self._tn.to(self.dev, torch.int32)
+        self._hfaces = torch.as_tensor(hand_faces).to(self.dev, torch.int32)
+        if self._tfaces.dim() != 3 or self._tfaces.shape[0] != templates.shape[0] or self._tn.shape != (templates.shape[0],):
+            raise ValueError(f"template_faces {tuple(self._tfaces.shape)} for {templates.shape[0]} templates")
+
+
 def predicted_pair(out, meta, obj_cls, evaluator):
     """The PREDICTED pair of every sample in the camera frame: hand = the predicted MANO mesh (the IK variant: its solved mesh) +
     mano_root, object = the template obj_cls turned and moved by the mean predicted rotation and translation + obj_center_cam.
-    ``evaluator``: a metrics.Evaluator built with template_faces / hand_faces.
+    ``evaluator``: a metrics.Evaluator built with template_faces / hand_faces, or a ``PairSource``.
     -> hand (B, 778, 3), hand faces (Fh, 3), obj (B, V, 3), obj faces (B, F, 3), obj face counts (B,), used (B,) bool: obj_cls >= 0
     (a sample that is not used borrows template 0)"""
     from .metrics import batch_rodrigues

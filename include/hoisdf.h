@@ -1312,6 +1312,53 @@ int hoisdf_eval_surface(const float* pred_verts, const int32_t* pred_n_verts, in
                         int n_samples, uint64_t seed, float* pred_to_gt, float* gt_to_pred, float* chamfer, int32_t* n_used,
                         float* samples_out, int32_t* nearest_out, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- field fit: a point set moved, as a rigid body, onto the zero level set of a sampled signed-distance field ------------------
+ * reference: none - the reference never feeds its fields back into the pose.  Grasping Field, AlignSDF and gSDF, which its field
+ * code descends from, fit the predicted mesh to the predicted field at test time.  csrc/field_fit.hip (the launches and the
+ * summation order) and csrc/field_fit_rules.h (the rules as plain functions, compiled for the host too);
+ * hoisdf_amd/field_fit_oracle.py states the rules in full - order of every operation included - and restates them in numpy
+ * float64.  A damped Gauss-Newton (Levenberg-Marquardt) fit per sample; rigid only; no gradient.  All arithmetic is fp64 on the
+ * f32 inputs, every product and sum rounded on its own, every sum in one order: two calls give the same bits, and a sample of a
+ * batch gets the bits it gets alone.
+ *
+ * hoisdf_field_fit (hoisdf_field_fit_launch_count(iters) = iters + 2 launches on `stream`, never synchronises):
+ *   values [B][ld] floats, ld >= n^3: the field of sample b on its grid, node i = ix + n (iy + n iz) at values[b ld + i];
+ *   grid [B][8] = lo xyz, cell xyz, 0, 0; n in 2 .. HOISDF_ISO_MAX_GRID: what hoisdf_iso_extract takes.  points [B][V][3] in the
+ *   frame of the field (V <= 2^24); n_points [B] DEVICE int32 or NULL = V, clamped to 0 .. V: rows beyond are not read, and their
+ *   rows of points_out are not written.  pivot [B][3] or NULL = the mean of the sample's points.
+ *   Pose: x = R (p - c) + c + t from R = I, t = 0.  A point TAKES PART when it lies on the grid (0 <= u <= n - 1 per axis, a NaN
+ *   fails) and the 8 corners of its cell are finite.  Cost: the mean over those points of the Huber function (threshold `huber` >
+ *   0, field units) of the trilinear interpolant f.  Step: J = [g, r x g] with g the interpolant's analytic gradient and r the
+ *   rotated offset (a left perturbation about c + t); (H + lambda diag(H) + 1e-12 I) d = -b by a 6 x 6 Cholesky factorisation, a
+ *   pivot that is not > 0 counting as a rejected step; R' = exp(omega) R by Rodrigues, t' = t + delta.  ACCEPT when the trial has
+ *   a point, 100 n_used >= min_used_percent x the start pose's n_used and the cost is strictly smaller: lambda <- max(lambda / 10,
+ *   1e-9); otherwise lambda <- 10 lambda, and the sample stops once lambda > 1e9.  lambda starts at lambda0 (>= 0).  The stop
+ *   test comes before a step is tried: after `iters` (0 .. HOISDF_FIELD_FIT_MAX_ITERS) tried steps, rejected ones included, or
+ *   when the solved step is below step_tol (max of |delta| and |omega| x the largest |p - c|).  A stopped sample does not change.
+ *   Launches: one workgroup of 256 lanes per sample.  init: pivot, extent, the sums of the start pose, the first plan (stop
+ *   tests, solve, trial pose).  round x iters: the sums at the trial pose, accept / reject, the next plan; the workgroup of a
+ *   stopped sample returns at once.  finish: the outputs.  The iteration is the host's fixed sequence of launches: no kernel has
+ *   a barrier inside a loop.  Sums: lane l takes points l, l + 256, ... ascending, an xor tree over 32 .. 1 within each wave of
+ *   64, then ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   Outputs: rot [B][9] (row-major), trans [B][3], points_out [B][V][3] = ((R (p - c) + c) + t) as floats, each rounded once from
+ *   fp64; cost [B][2] doubles = the start pose's and the final cost; info [B][4] int32 = points that take part at the start, at
+ *   the end, steps tried, steps accepted.  A sample with no point taking part at the start: R = I, t = 0, cost 0, info 0.
+ *   Optional (NULL: skipped): normal_out [B][56] doubles = the start pose's 28 sums (H's upper triangle row-major, b, cost, each
+ *   divided by n_used) and the same 28 sums over the terms' magnitudes; pose64_out [B][12] doubles = R and t unrounded.
+ *   Checked before any launch (HOISDF_ERR_INVALID, the argument named in hoisdf_last_error): a required pointer null (values,
+ *   grid, points, rot, trans, points_out, cost, info, workspace), B < 0 or > 65535, n, iters, V out of range, ld < n^3, huber not
+ *   > 0, a negative lambda0 or step_tol, min_used_percent outside 0 .. 100, a workspace below
+ *   hoisdf_field_fit_workspace_bytes(B) device bytes (-1 on an invalid B) or not aligned to 8 bytes.  B = 0 returns 0 with nothing
+ *   launched.  The workspace holds the per-sample state in fp64 (pivot, extent, R, t, lambda, the 28 current sums, the trial
+ *   pose, the counters, a status word); nothing in it needs to survive the call. */
+#define HOISDF_FIELD_FIT_MAX_ITERS 64
+long hoisdf_field_fit_workspace_bytes(int B);
+int hoisdf_field_fit_launch_count(int iters);
+int hoisdf_field_fit(const float* values, long ld, const float* grid, int n, const float* points, int V, const int32_t* n_points,
+                     const float* pivot, int B, int iters, float huber, float lambda0, float step_tol, int min_used_percent,
+                     float* rot, float* trans, float* points_out, double* cost, int32_t* info, double* normal_out,
+                     double* pose64_out, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- raster: which pixels the posed hand mesh and the posed object mesh cover - ids, depth, modal masks, overlays, silhouette IoU ----
  * reference: none - the reference reads its masks from per-frame image files and never renders a mesh.  csrc/raster.hip;
  * hoisdf_amd/raster_oracle.py restates the rules below in numpy and reproduces every output bit for bit.  A z-buffered triangle

@@ -16,6 +16,7 @@ import torch
 from hoisdf_amd import metrics as M
 from hoisdf_amd.config import cfg
 from hoisdf_amd.engine import SyntheticDataset, Tester, native_image_enabled
+from hoisdf_amd.refine import enabled as refine_enabled
 
 JOINTS_SIMPLE_TO_MANO = M.JOINTS_SIMPLE_TO_MANO            # the order of the HO3D submission file
 
@@ -44,6 +45,10 @@ def parse_args():
     ap.add_argument("--field-surface", action="store_true",
                     help="also extract the zero level set of the two learned fields (Model.field_surface, hoisdf_iso_extract) and report "
                          "their Chamfer distance to the ground-truth meshes (cfg.eval_field); procedural MESHES as templates")
+    ap.add_argument("--refine", action="store_true",
+                    help="also move the predicted hand and object, each as a rigid body, onto the zero level set of the field the network "
+                         "predicts (hoisdf_field_fit, cfg.eval_refine) and report the vertex errors before and after; procedural MESHES "
+                         "as templates")
     ap.add_argument("--silhouette", action="store_true",
                     help="also report the IoU of the predicted hand's and object's rendered silhouettes against the mask targets "
                          "(hoisdf_raster_meshes, cfg.eval_silhouette); procedural MESHES as templates")
@@ -69,6 +74,7 @@ def main():
     cfg.eval_interaction = bool(a.interaction)
     cfg.eval_field = bool(a.field_surface)
     cfg.eval_silhouette = bool(a.silhouette)
+    cfg.eval_refine = bool(a.refine)
     cfg.overlay_dir = a.overlay or ""
     # one process drives one GPU: the first id of --gpu_ids (the reference wraps the model in DataParallel over all of them)
     dev = torch.device("cuda", int(a.gpu_ids.split(",")[0]))
@@ -83,16 +89,22 @@ def main():
     templates = (0.05 * torch.randn(4, 500, 3, generator=g)).to(dev)         # stand-ins for the YCB models
     ho3d = cfg.dataset == "ho3d"
     faces = None
-    if M.interaction_enabled(cfg) or M.field_enabled(cfg) or M.silhouette_enabled(cfg) or cfg.overlay_dir:   # point clouds have no inside and no surface: closed procedural meshes instead
+    refine = refine_enabled(cfg)
+    if M.interaction_enabled(cfg) or M.field_enabled(cfg) or M.silhouette_enabled(cfg) or refine or cfg.overlay_dir:   # point clouds have no inside and no surface: closed procedural meshes instead
         from hoisdf_amd.sdf_data import procedural_templates
         faces = procedural_templates(device=dev)
         templates = faces["verts"]
     ev = M.Evaluator(cfg, templates, native=M.native_metrics_enabled(cfg), template_faces=faces,
                      hand_faces=mano_layer.th_faces if faces is not None else None)
+    if refine:                                             # the eval forward poses the predicted pair from the same templates
+        from hoisdf_amd.render import PairSource
+        tester.model.set_refine_source(PairSource(cfg, templates, faces, mano_layer.th_faces))
     for it, (inputs, targets, meta) in enumerate(loader):
-        out = tester.predict(inputs, targets, meta, mano_layer=mano_layer)
         B = meta["mano_root"].shape[0]
         obj_cls = (torch.arange(B) + it) % templates.shape[0]
+        if refine:
+            meta["obj_cls"] = obj_cls
+        out = tester.predict(inputs, targets, meta, mano_layer=mano_layer)
         ev.feed(out, targets, meta, obj_cls)
         if cfg.overlay_dir:
             from hoisdf_amd.render import write_overlays
